@@ -24,6 +24,11 @@ baselines (rank 0 at N=1, outside the timed region): cpu_baseline = the oracle (
           restatement) on the first 16 chunks of the frame with every host thread this job may use;
           torch_gpu_baseline = the same restatement with PyTorch-ROCm on this GPU over the whole frame
           (BASELINE.md §3's denominator of the 30x target) -> vs_baseline.
+plain / --full: a plain run (``bench.py --gpus 1 --steps K --warmup W``) sets up, warms up, times the K
+          steps and prints the result line (headline keys and the roofline of the timed kernel). The
+          other precisions of the same frame, render_s, the side legs (configs 3-5, mesh, animation)
+          and both baselines (cpu_baseline + PSNR, torch_gpu_baseline -> vs_baseline) run under
+          ``--full`` only. ``--dump-outputs DIR`` writes the last timed step's outputs as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -62,6 +67,15 @@ def parse():
     ap.add_argument('--steps', type=int, default=5)
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--rays', type=int, default=512 * 512)
+    ap.add_argument('--full', action='store_true',
+                    help='also run everything beside the headline figure: the other precisions of the same frame, '
+                         'the render_s leg, the side legs (train_step / sdf_render / sdf_train_step / mesh_extract / '
+                         'anim_step), cpu_baseline + PSNR and the PyTorch-ROCm denominator (vs_baseline); each can '
+                         'still be switched off with its --no-* option. Without --full a run sets up, warms up, '
+                         'times --steps steps and prints the result line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last timed step returned as DIR/<name>.npy '
+                         '(float32 / float64; an output above 8 MB as a fixed seeded sample of its rows)')
     ap.add_argument('--cpu-rays', type=int, default=16 * 2048)
     ap.add_argument('--no-cpu', action='store_true')
     ap.add_argument('--mode', choices=('render', 'train', 'sdf', 'sdf-train', 'mesh', 'anim'), default='render',
@@ -104,7 +118,34 @@ def parse():
                     help='training GEMM operand precision (config 3 is bf16: bf16_all = every GEMM on bf16 operands; '
                          'bf16 = the pose-space blend-weight MLP kept at fp32 level; both hold the config-3 PSNR gate, '
                          'tests/test_gpu_config3.py; fp32 = exact reference arithmetic)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure alone
+        args.no_cpu = args.no_exact = args.no_side = args.no_host_render = args.no_torch_baseline = True
+    return args
+
+
+DUMP_CAP_BYTES = 8 << 20  # per array
+DUMP_TOTAL_BYTES = 60 << 20  # of one dump (the arrays; .npy headers are ~128 B each)
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: every tensor of ``outputs`` as DIR/<name>.npy, float32 (float64 for float64 and
+    integer tensors). An array above the per-array cap (DUMP_CAP_BYTES, less when the dump has more than
+    seven arrays: DUMP_TOTAL_BYTES in all) is written as a sample of its rows (last dimension kept), drawn
+    without replacement by a generator seeded with 0 and sorted, so two runs with the same arguments
+    write the same rows."""
+    os.makedirs(directory, exist_ok=True)
+    cap = min(DUMP_CAP_BYTES, DUMP_TOTAL_BYTES // max(1, len(outputs)))
+    for name, t in outputs.items():
+        t = torch.as_tensor(t).detach()
+        t = t.to(torch.float32 if t.dtype in (torch.float32, torch.float16, torch.bfloat16) else torch.float64)
+        if t.numel() * t.element_size() > cap and t.dim() > 0:
+            rows = t.reshape(-1, t.shape[-1]) if t.dim() > 1 else t.reshape(-1)[:, None]
+            keep = max(1, cap // (rows.shape[1] * t.element_size()))
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=keep, replace=False))
+            sample = rows[torch.from_numpy(idx).to(rows.device)]
+            t = sample[:, 0] if t.dim() == 1 else sample
+        np.save(os.path.join(directory, name + '.npy'), t.cpu().numpy())
 
 
 def host_threads():
@@ -293,6 +334,8 @@ def main():
     out, dt_max, kernel_ms, (n_kept, m_rows) = timed(prec)
     clocks = {prec: timed.clock_mhz}
     progress(f'{prec}: {dt_max / args.steps * 1e3:.2f} ms/frame, kernel {kernel_ms:.2f} ms, clock {timed.clock_mhz:.0f} MHz')
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
     value = R * 64 * args.steps * frames / dt_max
     result = {
         'metric': METRIC, 'value': value, 'unit': 'ray-samples/s', 'n_gpus': world, 'steps': args.steps,
@@ -382,7 +425,7 @@ def profile_read(lib):
 
 
 def side_legs(args, rank, world, dev):
-    """Configs 3-5 timed inside the default run (so the driver's own bench call measures them too):
+    """Configs 3-5 timed inside a --full run (so one bench call measures them too):
     'train_step' (config 3 at N = 1, config 4 at N > 1: the training iteration with its RCCL gradient
     all-reduce), and at N = 1 'sdf_render' (config 5's network, bf16x6 fp32-level render of a 512x512
     frame, exact fp32 beside it) and 'sdf_train_step' (config 5's training iteration, exact fp32); at
@@ -394,6 +437,7 @@ def side_legs(args, rank, world, dev):
     def leg(fn, key, **over):
         a = copy.copy(args)
         a.no_cpu = True
+        a.dump_outputs = None  # the dump is the headline path's
         for k, v in over.items():
             setattr(a, k, v)
         t0 = time.perf_counter()
@@ -494,6 +538,8 @@ def bench_train(args, rank, world, dev, emit=True):
         dist.barrier()
     dt = time.perf_counter() - t0
     dt_max = max_over_ranks(dt, dev, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': step.loss3})  # what step() returned, before the profiled steps
     # the in-kernel shader clock (anr_profile_read_clock: entry / exit stamps of the fused chain launches)
     # over 3 more steps profiled after the timed ones, so events and stamps stay out of the timed region
     step.lib.anr_profile_enable(1)
@@ -612,6 +658,8 @@ def bench_sdf(args, rank, world, dev, emit=True):
 
     prec = args.sdf_precision
     out, dt_max, n_kept = timed(prec, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: v for k, v in out.items() if torch.is_tensor(v)})
     progress(f'sdf {prec}: {dt_max / args.steps * 1e3:.2f} ms/frame, clock {timed.net["clock_mhz"]}')
     dtypes = {'fp32': 'fp32', 'bf16x6': 'bf16 MFMA operands (hi/mid/lo split, 6 products per MAC: fp32-level), fp32 accumulate',
               'bf16x3': 'bf16 MFMA operands (hi/lo split, 3 products per MAC), fp32 accumulate'}
@@ -720,6 +768,8 @@ def bench_sdf_train(args, rank, world, dev, emit=True):
     if world > 1:
         dist.barrier()
     dt_max = max_over_ranks(time.perf_counter() - t0, dev, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': step.loss8})  # what step() returned, before the profiled steps
     # in-kernel clock of the step's k_lgemm layer products (exact fp32 F32 kernels), 2 profiled steps after
     # the timed ones
     step.lib.anr_profile_enable(1)
@@ -815,6 +865,8 @@ def bench_mesh(args, rank, world, dev, emit=True):
         dist.barrier()
     dt = time.perf_counter() - t0
     dt_max = max_over_ranks(dt, dev, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'alpha': alpha, 'vertices': verts, 'triangles': tris})
     alpha_ms = sum(ev[2 * j].elapsed_time(ev[2 * j + 1]) for j in range(args.steps)) / args.steps
     n_kept = int(renderer._aws[:4].view(torch.int32).item())  # anr_alpha_counts: kept points
     split = args.render_precision in ('bf16x3', 'bf16x6')
@@ -899,6 +951,8 @@ def bench_anim(args, rank, world, dev, emit=True):
     if world > 1:
         dist.barrier()
     dt_max = max_over_ranks(time.perf_counter() - t0, dev, world)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': st.loss3})
     pts = 2 * 65536
     result = {
         'metric': 'animation-stage points/s (2 x 65,536 sampled points per step, novel_pose_bw training)',

@@ -5,6 +5,8 @@
 #   tests[=PATTERN]   pytest -m gpu (optionally -k PATTERN; _or_ = ' or ', _and_ = ' and ') -> gpurun_out/TAG_gpu_tests.log
 #   smoke             __graft_entry__.smoke()                          -> TAG_smoke.log
 #   bench[:ARGS]      python bench.py ARGS (ARGS comma-separated)      -> TAG_bench[_MODE].log
+#                     (bench / prof / trace / ab: put --full into ARGS for the other precisions, render_s,
+#                     the side legs and the baselines; without it the headline steps alone run)
 #   prof[:ARGS]       rocprofv3 --kernel-trace --stats of bench ARGS  -> TAG_prof[_MODE]/
 #   pmc:KERNEL[:ARGS] FETCH_SIZE and WRITE_SIZE passes of bench ARGS, summarised for KERNEL into
 #                     profiles/pmc_latest.json (tools/pmc_traffic.py)  -> TAG_pmc_KERNEL_{f,w}/
