@@ -34,7 +34,7 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_sdf_network_train_workspace_bytes', 'anr_sdf_network_train_fwd', 'anr_sdf_network_train_counts',
            'anr_sdf_network_train_rows', 'anr_sdf_network_train_bwd', 'anr_sdf_points_workspace_bytes', 'anr_sdf_points',
            'anr_sample_volume', 'anr_knn_blend_workspace_bytes', 'anr_knn_blend', 'anr_sdf_mesh_pose',
-           'anr_last_error', 'anr_version')
+           'anr_train_deterministic', 'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
 
@@ -245,6 +245,7 @@ def load():
     lib.anr_profile_read.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     lib.anr_profile_read_clock.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
                                            ctypes.POINTER(ctypes.c_double)]
+    lib.anr_train_deterministic.argtypes = [ctypes.c_int]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)
@@ -256,6 +257,28 @@ def check(rc, what):
     if rc != 0:
         msg = _lib.anr_last_error().decode() if _lib is not None else ''
         raise RuntimeError(f'{what} failed (code {rc}): {msg}')
+
+
+class deterministic:
+    """Scope of the library's deterministic training mode (``anr_train_deterministic``): sets the
+    process-wide mode on entry and restores the value that was in force on exit, so callers in
+    different modes can coexist in one process. ``on=None`` leaves the mode alone."""
+
+    def __init__(self, on):
+        self.on = on
+        self.prev = None
+
+    def __enter__(self):
+        if self.on is not None:
+            self.prev = load().anr_train_deterministic(1 if self.on else 0)
+            if self.prev < 0:
+                raise RuntimeError(f'anr_train_deterministic failed (code {-self.prev})')
+        return self
+
+    def __exit__(self, *exc):
+        if self.prev is not None:
+            load().anr_train_deterministic(self.prev)
+        return False
 
 
 def stream_ptr(device=None):

@@ -111,6 +111,10 @@ __device__ __forceinline__ void rowsum_flush(const GemmArgs& g, int m0, float (&
     for (int e = 0; e < 4; ++e) {
       const int m = m0 + 4 * lane + e;
       if (m < M) {
+        if (g.rs_part) {  // deterministic split-K: this wave's partial, summed in order by k_gemm_det_reduce
+          g.rs_part[(long)(4 * blockIdx.z + (tid >> 6)) * g.rs_ld + m] = rsum[e];
+          continue;
+        }
         atomicAdd(g.rowsum + m, rsum[e]);
         if (g.rowsum2) atomicAdd(g.rowsum2 + m, rsum[e]);
       }
@@ -135,6 +139,10 @@ __device__ __forceinline__ void epilogue(const GemmArgs& g, const f32x4 (&acc)[2
         float* c = g.C + (long)m * g.ldc + n;
         if (g.atomic) {
           if (g.bias && first_split) v += g.bias[n];
+          if (g.part) {  // deterministic split-K: the split's partial, summed in order by k_gemm_det_reduce
+            g.part[(long)blockIdx.z * g.part_stride + (long)m * g.N + n] = v;
+            continue;
+          }
           atomicAdd(c, v);
           continue;
         }
@@ -600,6 +608,51 @@ void launch_gemm(GemmArgs g, dim3 grid, hipStream_t s) {
               (!g.softplus || !g.deriv || (g.ldd % 4 == 0 && al16(g.deriv)));
   if (sw) launch_gemm_sw<true>(g, grid, s, a_k, b_k);
   else launch_gemm_sw<false>(g, grid, s, a_k, b_k);
+}
+
+// ------------------------------------------------------------------------------------------
+// deterministic split-K (the training executor's fixed-order mode): the splits store their partial
+// tiles / row sums (GemmArgs::part, rs_part) and this kernel adds them in split order. One thread per
+// element of C, and the first M threads one row sum each; only the live splits (those below the device
+// sample count) were written and only they are read.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_gemm_det_reduce(GemmArgs g) {
+  const int K0 = g.K_dev ? *g.K_dev : g.seg[0].K;
+  const int live = min(g.ksplit, (K0 + g.kper - 1) / g.kper);
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u < (long)g.M * g.N) {
+    float t = 0.f;
+    for (int z = 0; z < live; ++z) t += g.part[(long)z * g.part_stride + u];
+    g.C[(u / g.N) * g.ldc + u % g.N] += t;
+  }
+  if (g.rowsum && u < g.M) {
+    float t = 0.f;
+    for (int q = 0; q < 4 * live; ++q) t += g.rs_part[(long)q * g.rs_ld + u];
+    g.rowsum[u] += t;
+    if (g.rowsum2) g.rowsum2[u] += t;
+  }
+}
+
+size_t gemm_det_floats(int M, int N, int ksplit) {
+  const size_t rs_ld = (size_t)(M + 63) / 64 * 64;
+  return (size_t)ksplit * ((size_t)M * N + 4 * rs_ld);
+}
+
+int launch_gemm_det(GemmArgs g, int M, float* scratch, size_t scratch_floats, hipStream_t s) {
+  if (M <= 0 || g.N <= 0) return 0;
+  if (g.ksplit < 1) g.ksplit = 1;
+  if (!scratch || !g.atomic || g.kper <= 0 || g.nseg != 1 || g.bias || g.M_dev ||
+      gemm_det_floats(M, g.N, g.ksplit) > scratch_floats)
+    return -1;
+  g.M = M;
+  g.part = scratch;
+  g.part_stride = (long)M * g.N;
+  g.rs_ld = (M + 63) / 64 * 64;
+  g.rs_part = g.rowsum ? scratch + (size_t)g.ksplit * g.part_stride : nullptr;
+  launch_gemm(g, dim3((g.N + 63) / 64, (M + 63) / 64, g.ksplit), s);
+  const long nred = (long)M * g.N;
+  hipLaunchKernelGGL(k_gemm_det_reduce, dim3((unsigned)((nred + 255) / 256)), dim3(256), 0, s, g);
+  return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 }  // namespace anr

@@ -891,6 +891,72 @@ __global__ void k_wgrad_reduce_group(WGradGroup G) {
   wgrad_reduce_at(G.d[k], (b - G.rstart[k]) * blockDim.x + threadIdx.x);
 }
 
+// Fixed-order form (the executor's deterministic mode): one thread owns an output float4 (4 rows of one
+// column) and adds all nz partial slabs in ascending sample-range order, then adds the sum into dW with
+// one plain read-modify-write; the first nout threads do the same for one column sum each (bsum, bsum2).
+// Every range's slab was written by the product kernel (an empty trailing range stores zeros), so nothing
+// stale is read. No two threads of a launch share an output: the host puts products that share a dW /
+// bsum / bsum2 target into consecutive launches (descriptor order), and launches are stream-ordered.
+__device__ __forceinline__ void wgrad_reduce_det_at(const WGrad& g, int u) {
+  const int per_tile = 4 * 16 * 64;
+  if (u < g.tiles * per_tile) {
+    const int t = u / per_tile, rem = u - t * per_tile;
+    const int w = rem / (16 * 64), ab = (rem / 64) & 15, lane = rem & 63;
+    const int a = ab >> 2, b = ab & 3;
+    const int ti = t / g.tj, tj = t - ti * g.tj;
+    const int i = ti * WG_T + (w >> 1) * 64 + 16 * a + 4 * (lane >> 4);
+    const int j = tj * WG_T + (w & 1) * 64 + 16 * b + (lane & 15);
+    if (j < g.K && j >= g.j0 && i < g.nout) {
+      const float* p = g.slab + ((long)t * 4 + w) * 16 * 256 + ab * 256 + lane * 4;
+      const long zs = (long)g.tiles * 4 * 16 * 256;  // floats from one range's slabs to the next
+      f32x4 s = {0.f, 0.f, 0.f, 0.f};
+      for (int z = 0; z < g.nz; ++z) s += *(const f32x4*)(p + z * zs);
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (i + r < g.nout) g.dW[(long)(i + r) * g.ldw + j] += s[r];
+    }
+  }
+  if (g.rs_slab && u < g.nout) {
+    float t = 0.f;
+    for (int z = 0; z < g.nz; ++z) t += g.rs_slab[(long)z * 256 + u];
+    if (g.bsum) g.bsum[u] += t;
+    if (g.bsum2) g.bsum2[u] += t;
+  }
+}
+static int wgrad_reduce_det_blocks(const WGrad& g) { return (std::max(g.tiles * 4 * 16 * 64, g.nout) + 255) / 256; }
+
+__global__ __launch_bounds__(256) void k_wgrad_reduce_det(WGradGroup G) {
+  const int b = blockIdx.x;
+  int k = 0;
+  while (k + 1 < G.n && b >= G.rstart[k + 1]) ++k;
+  wgrad_reduce_det_at(G.d[k], (b - G.rstart[k]) * blockDim.x + threadIdx.x);
+}
+
+// the fixed-order reductions of descriptors d[0..n): as few launches as keep every output with one writer
+// per launch, the writers of a shared output in descriptor order
+static void launch_wgrad_reduce_det(const WGrad* d, int n, hipStream_t s) {
+  WGradGroup B{};
+  auto flush = [&]() {
+    if (B.n) hipLaunchKernelGGL(k_wgrad_reduce_det, dim3(B.rstart[B.n]), dim3(256), 0, s, B);
+    B = WGradGroup{};
+  };
+  auto same = [](const float* a, const float* b) { return a && a == b; };
+  for (int k = 0; k < n; ++k) {
+    const WGrad& g = d[k];
+    bool clash = false;
+    for (int q = 0; q < B.n && !clash; ++q) {
+      const WGrad& h = B.d[q];
+      clash = g.dW == h.dW || same(g.bsum, h.bsum) || same(g.bsum, h.bsum2) || same(g.bsum2, h.bsum) ||
+              same(g.bsum2, h.bsum2);
+    }
+    if (clash) flush();
+    B.d[B.n] = g;
+    B.rstart[B.n + 1] = B.rstart[B.n] + wgrad_reduce_det_blocks(g);
+    ++B.n;
+  }
+  flush();
+}
+
 // ------------------------------------------------------------------------------------------
 // k_wgrad_dma: the bf16 x bf16 weight gradients of a group (the bulk of the bf16 training backward),
 // one workgroup per (product, sample range) owning the whole <= 256 x 256 dW: 8 waves of 64 outputs x
@@ -1193,7 +1259,7 @@ static int wgrad_reduce_blocks(const WGrad& g) {
 
 size_t wgrad_slab_floats() { return (size_t)WG_MAX_Z * 4 * WG_TILE_FLOATS + (size_t)WG_MAX_Z * 256; }
 
-int launch_wgrad(WGrad g, int n_host, hipStream_t s) {
+int launch_wgrad(WGrad g, int n_host, hipStream_t s, bool det) {
   if (n_host <= 0) return 0;
   const int ti = (g.nout + WG_T - 1) / WG_T, tj = (g.K + WG_T - 1) / WG_T;
   g.tj = tj;
@@ -1213,7 +1279,8 @@ int launch_wgrad(WGrad g, int n_host, hipStream_t s) {
   else if (g.ybf) hipLaunchKernelGGL((k_wgrad<false, true, false>), grid, dim3(256), 0, s, g);
   else if (g.xbf) hipLaunchKernelGGL((k_wgrad<false, false, true>), grid, dim3(256), 0, s, g);
   else hipLaunchKernelGGL((k_wgrad<false, false, false>), grid, dim3(256), 0, s, g);
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(wgrad_reduce_blocks(g)), dim3(256), 0, s, g);
+  if (det) launch_wgrad_reduce_det(&g, 1, s);
+  else hipLaunchKernelGGL(k_wgrad_reduce, dim3(wgrad_reduce_blocks(g)), dim3(256), 0, s, g);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
@@ -1231,7 +1298,8 @@ static bool wgrad_dma_fits(const WGrad& g) {
          ((uintptr_t)g.dY & 15) == 0 && ((uintptr_t)g.X & 15) == 0;
 }
 
-int launch_wgrad_group(const WGrad* d, int nd, int n_host, int nz, float* slab, size_t slab_floats, hipStream_t s) {
+int launch_wgrad_group(const WGrad* d, int nd, int n_host, int nz, float* slab, size_t slab_floats, hipStream_t s,
+                       bool det) {
   if (n_host <= 0 || nd <= 0) return 0;
   nz = nz < 8 ? 8 : (nz > WG_MAX_Z ? WG_MAX_Z : (nz + 7) / 8 * 8);
   WGradGroup G{};
@@ -1278,7 +1346,8 @@ int launch_wgrad_group(const WGrad* d, int nd, int n_host, int nz, float* slab, 
       else if (v == 3) hipLaunchKernelGGL((k_wgrad_group<false, false, true>), grid, dim3(256), 0, s, H);
       else hipLaunchKernelGGL((k_wgrad_group<false, false, false>), grid, dim3(256), 0, s, H);
     }
-    hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(G.rstart[G.n]), dim3(256), 0, s, G);
+    if (det) launch_wgrad_reduce_det(G.d, G.n, s);
+    else hipLaunchKernelGGL(k_wgrad_reduce_group, dim3(G.rstart[G.n]), dim3(256), 0, s, G);
     G = WGradGroup{};
     used = 0;
   };

@@ -58,12 +58,25 @@ struct GemmArgs {
   // by the workgroups of the first N tile; NULL: off
   float* rowsum;
   float* rowsum2;
+  // deterministic split-K (atomic launches only, NULL: off): split z stores its partial C tile to
+  // part[z * part_stride + m * N + n] and each wave its partial row sums to rs_part[(4 z + wave) * rs_ld + m]
+  // instead of the atomics; gemm_det_reduce then adds the live splits in split order into C / rowsum
+  float* part;
+  long part_stride;
+  float* rs_part;
+  int rs_ld;
   // per segment: the operand tiles may be read with 16-B loads (aligned base, stride a multiple of 4)
   int a_vec[2], b_vec[2];
   int vec_out;  // set by launch_gemm: non-atomic epilogue with 16-B accesses
 };
 
 void launch_gemm(GemmArgs g, dim3 grid, hipStream_t s);
+// deterministic split-K weight gradient (the generic kernel's fixed-order route): the launch of g (atomic,
+// ksplit splits of kper, M rows) with its partials in scratch, then k_gemm_det_reduce: one thread per
+// element of C (and of rowsum) adds the live splits in ascending order, then one plain add into C /
+// rowsum / rowsum2. -1: the scratch is too small (nothing launched)
+size_t gemm_det_floats(int M, int N, int ksplit);
+int launch_gemm_det(GemmArgs g, int M, float* scratch, size_t scratch_floats, hipStream_t s);
 
 // bf16 row GEMM with a weight-image B operand (anr_tgemm.hip): C[M][N] = epi(sum_s A_s[M][K_s] B_s^T),
 // A_s fp32 (or, abf, bf16) rows (stride lda elements, 16-B aligned, lda >= K_s rounded up to 64), B_s bf16 image rows
@@ -140,7 +153,7 @@ struct WGrad {
   int j0;        // k_wgrad_f32: columns j < j0 are not written (X starts j0 columns early, at a 16-B boundary)
 };
 size_t wgrad_slab_floats();
-int launch_wgrad(WGrad g, int n_host, hipStream_t s);
+int launch_wgrad(WGrad g, int n_host, hipStream_t s, bool det = false);
 // exact-fp32 weight gradient (k_wgrad_f32 + k_wgrad_reduce; fp32 rows, nout / K <= 256, 16-B addressable
 // rows): the exact executors' dW += dY^T X (+ bsum / bsum2 column sums), ACCUMULATED like the atomic
 // split-K GEMM it replaces; -1 (nothing launched) for a product it does not take
@@ -157,7 +170,11 @@ struct WGradGroup {
   int start[WG_GROUP_MAX + 1];   // first workgroup of descriptor k (k_wgrad_group)
   int rstart[WG_GROUP_MAX + 1];  // first reduce block of descriptor k (k_wgrad_reduce_group)
 };
-int launch_wgrad_group(const WGrad* d, int nd, int n_host, int nz, float* slab, size_t slab_floats, hipStream_t s);
+// det: the fixed-order reduction (k_wgrad_reduce_det: one thread per output float4 sums every sample range
+// in ascending order, then one plain add), products of a group that share a dW / bsum target reduced by
+// consecutive launches in descriptor order
+int launch_wgrad_group(const WGrad* d, int nd, int n_host, int nz, float* slab, size_t slab_floats, hipStream_t s,
+                       bool det = false);
 
 // fused chains of the bf16 training executor (anr_tchain.hip): program 0 = the blend-weight MLP forward
 // (9 layers), 1 = the canonical NeRF forward (8 layers + feature||alpha, latent, view, rgb), 2 / 3 their
@@ -281,6 +298,9 @@ struct TrainBufs {
   float* zero4;
   float* zero2048;
   float* loss3_out;
+  // deterministic mode (NULL: the atomic sums): k_tr_loss / k_an_loss store their per-block partial sums
+  // here ([y][block][2] / [block]) and k_det_sum adds them in block order
+  float* loss_part;
 };
 
 __global__ void k_tr_point_prep(TrainBufs b);
@@ -329,6 +349,14 @@ __global__ void k_an_set(int* c, int n);
 __global__ void k_an_loss_final(const float* acc, const int* rows, float* loss3);
 __global__ void k_adam(float* p, float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, float wd,
                        float bc1, float bc2_sqrt, float clip);
+// fixed-order sums of per-block partials: block q adds src[q][i * stride[q]], i < n[q], thread t its
+// entries t, t + 256, .. in ascending order, then a fixed tree over the threads; dst[q] += the sum
+struct DetSum {
+  const float* src[4];
+  int n[4], stride[4];
+  float* dst[4];
+};
+__global__ void k_det_sum(DetSum a);
 __global__ void k_tr_loss(TrainBufs b, const float* rgb_gt, const uint8_t* mask, float* acc3);
 __global__ void k_tr_loss_final(const float* acc3, const int* m_rows, float* loss3);
 __global__ void k_tr_loss_grads(TrainBufs b, const float* rgb_gt, const uint8_t* mask, const float* acc3, float* d_rgb,

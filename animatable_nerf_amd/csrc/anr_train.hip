@@ -248,7 +248,12 @@ __global__ __launch_bounds__(256) void k_tr_loss(TrainBufs b, const float* rgb_g
   if (threadIdx.x == 0) {
     const float s0 = sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
     const float s1 = sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
-    if (blockIdx.y == 0) {
+    if (b.loss_part) {  // deterministic mode: per-block partials, added in block order by k_det_sum
+      float* part = b.loss_part + 2 * ((long)blockIdx.y * gridDim.x + blockIdx.x);
+      part[0] = s0;
+      part[1] = s1;
+      if (blockIdx.y == 1 && blockIdx.x == 0) acc3[3] = (float)*b.m_rows;
+    } else if (blockIdx.y == 0) {
       atomicAdd(acc3 + 0, s0);
       atomicAdd(acc3 + 1, s1);
     } else {
@@ -256,6 +261,23 @@ __global__ __launch_bounds__(256) void k_tr_loss(TrainBufs b, const float* rgb_g
       if (blockIdx.x == 0) acc3[3] = (float)*b.m_rows;  // the rows count beside the sums (a ray split sums all four)
     }
   }
+}
+
+// deterministic mode's loss sums: block q of the launch adds n[q] partials (stride[q] apart) in a fixed
+// order — thread t its entries t, t + 256, .. ascending, then a fixed tree over the 256 threads — and adds
+// the result into dst[q] (one writer)
+__global__ __launch_bounds__(256) void k_det_sum(DetSum a) {
+  __shared__ float sh[256];
+  const int q = blockIdx.x, t = threadIdx.x;
+  float v = 0.f;
+  for (int i = t; i < a.n[q]; i += 256) v += a.src[q][(long)i * a.stride[q]];
+  sh[t] = v;
+  __syncthreads();
+  for (int off = 128; off > 0; off >>= 1) {
+    if (t < off) sh[t] += sh[t + off];
+    __syncthreads();
+  }
+  if (t == 0) *a.dst[q] += sh[0];
 }
 
 // acc3 = {sum sq. error, mask rays, sum smooth-L1, alpha_ind rows} (summed over the ranks of a ray split)
@@ -698,7 +720,8 @@ __global__ __launch_bounds__(256) void k_an_loss(TrainBufs b, float train_th, co
   if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = v; shc[threadIdx.x >> 6] = c; }
   __syncthreads();
   if (threadIdx.x == 0) {
-    atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
+    if (b.loss_part) b.loss_part[blockIdx.x] = sh[0] + sh[1] + sh[2] + sh[3];  // deterministic mode (k_det_sum)
+    else atomicAdd(acc, sh[0] + sh[1] + sh[2] + sh[3]);
     atomicAdd(rows, shc[0] + shc[1] + shc[2] + shc[3]);
   }
 }

@@ -6,6 +6,7 @@
 // count stays on the device (M_dev / K_dev in the GEMM arguments, capacity-sized grids), so no call
 // syncs with the host (the reference syncs ~6x per chunk).
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
@@ -29,12 +30,34 @@ constexpr int kWStreams = 2;
 // partial-slab floats per lane: a weight-gradient group of up to 16 products at 16 sample ranges
 const size_t kLaneFloats = 4 * wgrad_slab_floats();
 
+// ---- deterministic mode ---------------------------------------------------------------------------
+// anr_train_deterministic (process-wide) / ANR_TRAIN_DETERMINISTIC=1|0 (read per call, wins when set).
+// With the mode on every float accumulation of a step has a fixed order (DESIGN "Deterministic mode"):
+//  - every weight-gradient product, its reduction and the latent-row updates run on ONE stream (lane 0;
+//    the caller's under ANR_TRAIN_SERIAL) in issue order, so the adds into one gradient element are
+//    ordered by the stream whatever the executor's streams are;
+//  - the slab reductions are k_wgrad_reduce_det (all sample ranges in order, one plain add), products of
+//    a group that share a target in consecutive launches;
+//  - the generic split-K products store per-split partials (launch_gemm_det) instead of atomics;
+//  - the latent-row updates of a flush are one launch per post, in post order;
+//  - the loss kernels store per-block partials that k_det_sum adds in block order.
+std::atomic<int> g_train_det{0};
+int train_det() {
+  const char* v = getenv("ANR_TRAIN_DETERMINISTIC");
+  if (v && (v[0] == '0' || v[0] == '1') && v[1] == 0) return v[0] == '1';
+  return g_train_det.load(std::memory_order_relaxed);
+}
+// scratch of the deterministic split-K products: 512-sample splits of at most 256 x 256 outputs
+size_t det_scratch_floats(long N) { return gemm_det_floats(256, 256, (int)((N + 511) / 512)); }
+// per-block loss partials (k_tr_loss: 2 sums x 2 rows of blocks; k_an_loss: 1)
+size_t loss_part_floats(long N) { return (size_t)((N + 255) / 256) * 4; }
+
 // training workspace = render layout (prefix, incl. raw) + per-sample activations / gradients
 struct TLayout {
   Layout L;
   size_t pt, Gp, Ip, Gv, Lp, lbs, Gt, It, Lt, Hp, Ht, Hn, Feat, Alpha, Lat, View, Rgbl;
   size_t draw, dRgb, dAlpha, dA16, dBp, dBt, dLp, dLt, dIt, dGt, dGt2, dHn, dHt, dHp, dFeat, dLat, dView;
-  size_t ysum, acc3, d_rgb, d_pbw, d_tbw, wimg, wslab, tcimg, bitsP, bitsT, bitsN, total;
+  size_t ysum, acc3, d_rgb, d_pbw, d_tbw, wimg, wslab, tcimg, bitsP, bitsT, bitsN, lpart, dscr, dscr_floats, total;
 };
 
 // ReLU mask bits of one chain layer (TcArgs::bits): 32 B per sample, 128 rows past the last (a tile's
@@ -72,6 +95,10 @@ TLayout tlayout(int n_rays, int chunk, long np, long nt) {
   // (8 layers + view_fc)
   T.bitsP = take(8 * bits_stride((long)N) / 4); T.bitsT = take(8 * bits_stride((long)N) / 4);
   T.bitsN = take(9 * bits_stride((long)N) / 4);
+  // deterministic mode: per-block loss partials, per-split partials of the generic weight gradients
+  T.lpart = take(loss_part_floats((long)std::max(N, R)));
+  T.dscr_floats = det_scratch_floats((long)N);
+  T.dscr = take(T.dscr_floats);
   T.total = o;
   return T;
 }
@@ -239,6 +266,10 @@ struct Exec {
   // every launch is sized for the capacity `cap` and reads the count from n_dev
   const int* n_dev = nullptr;
   int cap = 0;
+  // deterministic mode (train_det(), read once per call): one weight-gradient stream, fixed-order reductions
+  int det = train_det();
+  float* dscr = nullptr;  // per-split partials of the generic weight gradients (det)
+  size_t dscr_floats = 0;
 
   int grid_n() const { return n_dev ? cap : n; }  // rows a per-sample launch covers
 
@@ -246,7 +277,7 @@ struct Exec {
   // a weight-gradient lane (stream + its partial-slab region), ordered after everything issued to s
   // so far; lane < 0: the next one round robin
   int wstream(hipStream_t* w, int* lane, int want = -1) {
-    const int l = want >= 0 ? want : (wnext++ % (ss ? ss->lanes : 1));
+    const int l = det ? 0 : want >= 0 ? want : (wnext++ % (ss ? ss->lanes : 1));
     *lane = ss ? l : 0;
     *w = ss ? ss->sw[l] : s;
     return order(ss, *w, s);
@@ -261,12 +292,19 @@ struct Exec {
     // (each lane its own slab region; the groups' dW / bias / latent updates are atomic adds), so one
     // group's reduction and small-format launches overlap the next group's products
     const char* al = getenv("ANR_WG_ALT_LANES");
-    const int fl = ss && al && al[0] == '1' ? (nflush++ % ss->lanes) : 0;
+    const int fl = ss && !det && al && al[0] == '1' ? (nflush++ % ss->lanes) : 0;
     hipStream_t w = ss ? ss->sw[fl] : s;
     for (int i = 0; i < npsrc; ++i) ANR_TRY(order(ss, w, pend_src[i]));
-    if (npend && launch_wgrad_group(pend, npend, grid_n(), group_nz, slab(fl), lane_floats, w) != 0)
+    if (npend && launch_wgrad_group(pend, npend, grid_n(), group_nz, slab(fl), lane_floats, w, det != 0) != 0)
       return check_launch("k_wgrad_group");
-    if (npost) {  // every latent-row update of the flush in one launch
+    if (npost && det) {  // posts can share dW latent columns and table rows: one launch each, in post order
+      for (int i = 0; i < npost; ++i) {
+        const LatentPost& q = post[i];
+        hipLaunchKernelGGL(k_tr_latent_grad, dim3(q.ncol + 128), dim3(128), 0, w, q.ys, q.W, q.in_ch, q.c0, q.ncol, q.tab,
+                           q.li, q.add, q.gW, q.gtab);
+      }
+      ANR_TRY(check_launch("k_tr_latent_grad"));
+    } else if (npost) {  // every latent-row update of the flush in one launch
       LatentPosts P{};
       for (int i = 0; i < npost; ++i) {
         const LatentPost& q = post[i];
@@ -422,7 +460,7 @@ struct Exec {
     ANR_TRY(wstream(&w, &lane, want_lane));
     if (fast) {
       wg.slab = slab(lane);
-      if (launch_wgrad(wg, grid_n(), w) != 0) return check_launch("k_wgrad");
+      if (launch_wgrad(wg, grid_n(), w, det != 0) != 0) return check_launch("k_wgrad");
       return ANR_OK;
     }
     if (bf) return fail(ANR_E_ARG, "train: bf16-stored operand off the weight-gradient path");
@@ -436,6 +474,12 @@ struct Exec {
     g.C = dW + c0; g.ldc = in_ch; g.atomic = 1;
     g.ksplit = (grid_n() + 511) / 512;  // 512 samples per split (measured: 1024 / 512 / 256 / 2048)
     g.kper = 512;
+    if (det) {  // the splits' partials to scratch, added in split order (no atomics)
+      g.bf16 = bf16;
+      if (launch_gemm_det(g, Nout, dscr, dscr_floats, w) != 0)
+        return fail(ANR_E_WORKSPACE, "train: deterministic weight gradient without scratch");
+      return check_launch("k_gemm (deterministic split-K)");
+    }
     return gemm(g, Nout, w);
   }
 
@@ -1146,7 +1190,7 @@ int train_backward(const anr_params* p, float* const* g, const anr_frame* f, con
 // ---- (f) animation stage: aninerf_animation_trainer.NetworkWrapper.forward + backward ----------
 struct ALayout {
   size_t counts, amax, acc, pt, Gp, Ip, Lp, Bp, lbs, Gt, It, Lt, Bt, Hp, Ht, Hn, Alpha, sel;
-  size_t dBp, dBt, dLp, dLt, dIt, dGt, dA, dB, ysum, fold, wimg, wslab, total;
+  size_t dBp, dBt, dLp, dLt, dIt, dGt, dA, dB, ysum, fold, wimg, wslab, lpart, dscr, dscr_floats, total;
 };
 
 ALayout alayout(long N) {
@@ -1168,6 +1212,9 @@ ALayout alayout(long N) {
   T.fold = take(1280 * 4);
   T.wimg = take(wimg_bytes());
   T.wslab = take(wgrad_slab_floats() * 4);
+  T.lpart = take(loss_part_floats(N) * 4);
+  T.dscr_floats = det_scratch_floats(N);
+  T.dscr = take(T.dscr_floats * 4);
   T.total = o;
   return T;
 }
@@ -1248,8 +1295,15 @@ int anim_path(const anr_params* p, float* const* grads, const anr_frame* f, cons
   }
   const int k = obs ? 0 : 1;
   hipLaunchKernelGGL(k_an_select, dim3(g1), dim3(256), 0, s, b, obs ? 1 : 0, o->norm_th, amax);
+  if (e.det) b.loss_part = (float*)(ws + T.lpart);  // per-block partials instead of the atomic sum
   hipLaunchKernelGGL(k_an_loss, dim3(g1), dim3(256), 0, s, b, o->train_th, (const unsigned long long*)amax, acc + k,
                      counts + 1 + k);
+  if (e.det) {
+    DetSum d{};
+    d.src[0] = b.loss_part; d.n[0] = g1; d.stride[0] = 1; d.dst[0] = acc + k;
+    hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(256), 0, s, d);
+    b.loss_part = nullptr;
+  }
   hipLaunchKernelGGL(k_an_loss_grads, dim3(g1), dim3(256), 0, s, b, (const int*)(counts + 1 + k), obs ? 1 : 0);
   ANR_TRY(check_launch("anim forward"));
   if (obs) {
@@ -1269,6 +1323,12 @@ int anim_path(const anr_params* p, float* const* grads, const anr_frame* f, cons
 }  // namespace
 
 extern "C" {
+
+int anr_train_deterministic(int on) {
+  if (on == -1) return g_train_det.load(std::memory_order_relaxed);
+  if (on != 0 && on != 1) return -fail(ANR_E_ARG, "anr_train_deterministic: on must be 0, 1 or -1");
+  return g_train_det.exchange(on, std::memory_order_relaxed);
+}
 
 size_t anr_train_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f) {
   if (!o || !f || n_rays <= 0) return 0;
@@ -1293,6 +1353,8 @@ int anr_train_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, c
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
   e.ss = om.ss;
   e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
                       !chains_cover(e, true, false)));
   ANR_TRY(train_forward(p, f, ray_o, ray_d, near_, far_, n_rays, o, out, ws, T, s, e));
@@ -1320,6 +1382,8 @@ int anr_train_bwd(const anr_params* p, float* const* grads, const anr_frame* f, 
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
   e.ss = om.ss;
   e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
                       !(chains_cover(e, false, true) && chain_bits_valid(ws))));
   ANR_TRY(train_backward(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, d_rgb_map, d_pbw, d_tbw, ws, T, s, e));
@@ -1354,6 +1418,8 @@ int train_step_body(const anr_params* p, float* const* grads, const anr_frame* f
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
   e.ss = ss;
   e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
                       !chains_cover(e, true, true)));
   float* acc3 = (float*)(ws + T.acc3);
@@ -1366,8 +1432,21 @@ int train_step_body(const anr_params* p, float* const* grads, const anr_frame* f
   if (!e.prezeroed && hipMemsetAsync(acc3, 0, 16, s) != hipSuccess) return fail(ANR_E_HIP, "memset");
   const long N = (long)n_rays * 64;
   const int gx = (int)((std::max<long>(n_rays, N) + 255) / 256);
+  if (e.det) b.loss_part = (float*)(ws + T.lpart);  // per-block partials instead of the atomic sums
   hipLaunchKernelGGL(k_tr_loss, dim3(gx, 2), dim3(256), 0, s, b, rgb_gt, mask_at_box, acc3);
   ANR_TRY(check_launch("k_tr_loss"));
+  if (e.det) {  // the partials in block order into the (zeroed) sums: squared error, mask rays, smooth-L1
+    DetSum d{};
+    for (int q = 0; q < 3; ++q) {
+      d.src[q] = b.loss_part + (q == 2 ? 2 * (long)gx : q);
+      d.n[q] = gx;
+      d.stride[q] = 2;
+      d.dst[q] = acc3 + q;
+    }
+    hipLaunchKernelGGL(k_det_sum, dim3(3), dim3(256), 0, s, d);
+    ANR_TRY(check_launch("k_det_sum"));
+    b.loss_part = nullptr;
+  }
   if (split) ANR_TRY(split->run(acc3, 4, ANR_REDUCE_SUM_F32, s));  // the batch's loss sums and row count
   b.loss3_out = loss3;  // the loss values (loss_final) from k_tr_loss_grads' first thread
   float* d_rgb = (float*)(ws + T.d_rgb);
@@ -1470,6 +1549,7 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
   key_add(key, *o);
   key_add(key, rgb_gt); key_add(key, mask_at_box); key_add(key, *out); key_add(key, loss3);
   key_add(key, workspace); key_add(key, ws_bytes);
+  key_add(key, train_det());  // a graph captured in one mode is never replayed in the other
   StepGraphs& G = step_graphs();
   std::lock_guard<std::mutex> lock(G.mu);
   for (size_t i = 0; i < G.cache.size(); ++i)
@@ -1558,6 +1638,8 @@ int anr_anim_step(const anr_params* p, float* const* grads, const anr_frame* f, 
   hipLaunchKernelGGL(k_prep, dim3(prep_blocks(0, 0)), dim3(256), 0, s, pa);
   ANR_TRY(check_launch("k_prep(anim)"));
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), wgrad_slab_floats(), true));
   ANR_TRY(anim_path(p, grads, f, wpts, n_obs, true, o, ws, T, s, e));
   ANR_TRY(anim_path(p, grads, f, tpts, n_can, false, o, ws, T, s, e));
@@ -1604,6 +1686,8 @@ int anr_network_train_fwd(const anr_params* p, const anr_frame* f, const anr_sam
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
   e.ss = om.ss;
   e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
                       !chains_cover(e, true, false)));
   ANR_TRY(train_forward(p, f, nullptr, nullptr, nullptr, nullptr, G, &oo, nullptr, ws, T, s, e, x));
@@ -1634,6 +1718,8 @@ int anr_network_train_bwd(const anr_params* p, float* const* grads, const anr_fr
   Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
   e.ss = om.ss;
   e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
                       !(chains_cover(e, false, true) && chain_bits_valid(ws))));
   ANR_TRY(train_backward(p, grads, f, nullptr, nullptr, nullptr, nullptr, G, &oo, nullptr, d_pbw, d_tbw, ws, T, s, e, x,

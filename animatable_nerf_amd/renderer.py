@@ -476,6 +476,13 @@ def to_host(ret):
     return out
 
 
+def _cfg_deterministic(cfg):
+    """cfg.train_deterministic for the autograd paths (NetworkWrapper): True switches the library's
+    deterministic training mode on around the backward call; False / absent leaves the mode alone (the
+    process-wide setter anr_train_deterministic and ANR_TRAIN_DETERMINISTIC still apply)."""
+    return True if cfg.get('train_deterministic', False) else None
+
+
 class _TrainRender(torch.autograd.Function):
     """forward = anr_train_fwd, backward = anr_train_bwd (parameter gradients accumulate)."""
 
@@ -509,9 +516,11 @@ class _TrainRender(torch.autograd.Function):
         grads = [torch.zeros_like(t) for t in params]
         gp = (ctypes.c_void_p * _lib.NUM_TENSORS)(*[g.data_ptr() for g in grads])
         keep = [t.contiguous() if t is not None else None for t in (d_rgb, d_pbw, d_tbw)]
-        _lib.check(lib.anr_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), *c.ray_ptrs(), c.R,
-                                     ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),
-                                     ctx.ws_bytes, _lib.stream_ptr(dev)), 'anr_train_bwd')
+        with _lib.deterministic(_cfg_deterministic(r.cfg)):
+            rc = lib.anr_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), *c.ray_ptrs(), c.R,
+                                   ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),
+                                   ctx.ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, 'anr_train_bwd')
         return (None, None, None, *grads)
 
 
@@ -544,9 +553,11 @@ class _TrainNetwork(torch.autograd.Function):
         grads = [torch.zeros_like(t) for t in params]
         gp = (ctypes.c_void_p * _lib.NUM_TENSORS)(*[g.data_ptr() for g in grads])
         keep = [t.contiguous() if t is not None else None for t in (d_raw, d_pbw, d_tbw)]
-        _lib.check(r.lib.anr_network_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), ctypes.byref(c.samples),
-                                               ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),
-                                               ctx.ws_bytes, _lib.stream_ptr(dev)), 'anr_network_train_bwd')
+        with _lib.deterministic(_cfg_deterministic(r.cfg)):
+            rc = r.lib.anr_network_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), ctypes.byref(c.samples),
+                                             ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),
+                                             ctx.ws_bytes, _lib.stream_ptr(dev))
+        _lib.check(rc, 'anr_network_train_bwd')
         return (None, None, None, *grads)
 
 

@@ -71,11 +71,19 @@ class FusedStep:
 
     ``step(batch)`` = forward + losses + backward (``anr_train_step``) + [RCCL all-reduce of the
     gradient blob] + clip_grad_value_(40) + Adam (``anr_adam``). Returns the device loss triple
-    (loss, img_loss, bw_loss) without synchronising.
+    (loss, img_loss, bw_loss) without synchronising. ``deterministic=True`` (default: the cfg key
+    ``train_deterministic``) runs the step in the library's deterministic mode.
     """
 
-    def __init__(self, net, cfg=None, lr=None, clip=40.0, betas=(0.9, 0.999), eps=1e-8, group=None, ray_split=False):
+    def __init__(self, net, cfg=None, lr=None, clip=40.0, betas=(0.9, 0.999), eps=1e-8, group=None, ray_split=False,
+                 deterministic=None):
         self.cfg = cfg if cfg is not None else _config.active()
+        # deterministic training mode (anr_train_deterministic; None: cfg.train_deterministic): every float
+        # sum of the step in a fixed order, so same weights + same batches give the same bits. Set around
+        # each step's library call and restored after it, so steps in different modes coexist in a process
+        # (the environment's ANR_TRAIN_DETERMINISTIC still wins inside the library). Under ray_split the
+        # result is deterministic only if the all-reduce is.
+        self.deterministic = bool(self.cfg.get('train_deterministic', False) if deterministic is None else deterministic)
         self.net = net
         self.renderer = Renderer(net, self.cfg)
         self.lib = self.renderer.lib
@@ -314,10 +322,15 @@ class FusedStep:
             hooks = self._hooks[hkey] = _lib.TrainHooks(self.nerf_ready.cuda_event if overlap else None, ray_offset,
                                                         self._reduce_cb, None)
         self._ws_now = ws
-        _lib.check(self.lib.anr_train_step_hooked(ctypes.byref(p), gp, ctypes.byref(c.frame), *c.ray_ptrs(), R,
-                                                  ctypes.byref(c.opts), _lib.ptr(rgb), _lib.ptr(mask),
-                                                  ctypes.byref(c.out), _lib.ptr(self.loss3), ctypes.byref(hooks),
-                                                  _lib.ptr(ws), ws_bytes, stream), 'anr_train_step_hooked')
+        prev = self.lib.anr_train_deterministic(1 if self.deterministic else 0)
+        try:
+            rc = self.lib.anr_train_step_hooked(ctypes.byref(p), gp, ctypes.byref(c.frame), *c.ray_ptrs(), R,
+                                                ctypes.byref(c.opts), _lib.ptr(rgb), _lib.ptr(mask),
+                                                ctypes.byref(c.out), _lib.ptr(self.loss3), ctypes.byref(hooks),
+                                                _lib.ptr(ws), ws_bytes, stream)
+        finally:
+            self.lib.anr_train_deterministic(prev)
+        _lib.check(rc, 'anr_train_step_hooked')
         # N > 1: the NeRF bucket's all-reduce runs beside the blend-weight backward, then the rest
         self.buckets.reduce(0, self.nerf_ready if overlap else None)
         self.buckets.reduce(1)

@@ -82,9 +82,12 @@ def anim_step(renderer, batch, grads, loss3, wvals, tvals):
     nbytes = lib.anr_anim_workspace_bytes(max(n0, n1))
     ws = renderer._workspace('_anws', nbytes, c.dev)
     gp = (ctypes.c_void_p * _lib.NUM_NOVEL_TENSORS)(*[g.data_ptr() for g in grads])
-    _lib.check(lib.anr_anim_step(ctypes.byref(p), gp, ctypes.byref(c.frame), _lib.ptr(c.wpts), n0, _lib.ptr(c.tpts),
-                                 n1, ctypes.byref(c.opts), _lib.ptr(loss3), _lib.ptr(ws), nbytes,
-                                 _lib.stream_ptr(c.dev)), 'anr_anim_step')
+    # cfg.train_deterministic: the library's deterministic training mode around the call (False: left alone)
+    with _lib.deterministic(True if renderer.cfg.get('train_deterministic', False) else None):
+        rc = lib.anr_anim_step(ctypes.byref(p), gp, ctypes.byref(c.frame), _lib.ptr(c.wpts), n0, _lib.ptr(c.tpts),
+                               n1, ctypes.byref(c.opts), _lib.ptr(loss3), _lib.ptr(ws), nbytes,
+                               _lib.stream_ptr(c.dev))
+    _lib.check(rc, 'anr_anim_step')
     return c
 
 

@@ -293,6 +293,23 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
                           const anr_render_opts* o, const float* rgb_gt, const uint8_t* mask_at_box,
                           const anr_render_out* out, float* loss3, const anr_train_hooks* hooks, void* workspace,
                           size_t ws_bytes, void* stream);
+/* anr_train_deterministic: the process-wide deterministic training mode (default 0). on = 1 / 0 sets it,
+ * on = -1 only queries; the return value is the mode in force BEFORE the call (0 or 1). Any other
+ * argument changes nothing and returns -ANR_E_ARG (negative, so it cannot be mistaken for a mode; the text
+ * via anr_last_error()). It makes no HIP call. The environment variable ANR_TRAIN_DETERMINISTIC=1|0, read
+ * at every training call, wins over the setter when it is set (precedence: environment, then this setter,
+ * then a binding's own default such as the Python cfg key train_deterministic).
+ * With the mode on, anr_train_step(_hooked), anr_train_bwd, anr_network_train_bwd and anr_anim_step
+ * produce gradients, loss3 and (through anr_adam) weights that are a function of the parameters, the batch,
+ * t_rand, the precision, the shapes and the gradient buffers' contents on entry only: bit-identical from
+ * run to run and whatever streams the executor uses (ANR_TRAIN_SERIAL, ANR_TRAIN_ON_CALLER, ANR_TRAIN_GRAPH).
+ * Every weight-gradient product and its reduction then run on one stream in issue order and every float
+ * sum has a fixed order (no floating-point atomics); switches that change the summation tree itself
+ * (ANR_WG_GROUP, ANR_WG_DMA, ANR_WG_GROUP_NZ, ANR_WG_FILL, ANR_WG_FLUSH_EVERY, the chain switches) give
+ * another, equally reproducible, result. With the mode off nothing changes.
+ * Not covered: sdf_pdf training (anr_sdf_train*), which ignores the mode; and under a ray split
+ * (anr_train_hooks.reduce) the result is deterministic only if the caller's all-reduce is. */
+int anr_train_deterministic(int on);
 int anr_adam(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
              float beta2, float eps, float weight_decay, int step, float clip_value, void* stream);
 
