@@ -34,7 +34,7 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_sdf_network_train_workspace_bytes', 'anr_sdf_network_train_fwd', 'anr_sdf_network_train_counts',
            'anr_sdf_network_train_rows', 'anr_sdf_network_train_bwd', 'anr_sdf_points_workspace_bytes', 'anr_sdf_points',
            'anr_sample_volume', 'anr_knn_blend_workspace_bytes', 'anr_knn_blend', 'anr_sdf_mesh_pose',
-           'anr_train_deterministic', 'anr_last_error', 'anr_version')
+           'anr_train_deterministic', 'anr_eval_workspace_bytes', 'anr_eval_frame', 'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
 
@@ -118,6 +118,20 @@ class SdfFrame(ctypes.Structure):
 class SdfRenderOut(ctypes.Structure):
     _fields_ = [('rgb_map', ctypes.c_void_p), ('acc_map', ctypes.c_void_p), ('depth_map', ctypes.c_void_p),
                 ('raw', ctypes.c_void_p), ('sdf', ctypes.c_void_p), ('tbounds_out', ctypes.c_void_p)]
+
+
+EVAL_NOUT = 12  # ANR_EVAL_NOUT: doubles of one anr_eval_frame record
+# indices into the record
+EVAL_SSE, EVAL_COUNT, EVAL_MSE, EVAL_PSNR, EVAL_SSIM, EVAL_X, EVAL_Y, EVAL_W, EVAL_H, EVAL_SUM_GT, EVAL_STATUS = range(11)
+EVAL_OK, EVAL_SKIPPED, EVAL_NARROW, EVAL_MISMATCH = 0, 1, 2, 3  # record[EVAL_STATUS]
+
+
+class EvalOpts(ctypes.Structure):
+    """anr_eval_opts: struct_size is filled in by the constructor; the defaults are the library's."""
+    _fields_ = [('struct_size', ctypes.c_size_t), ('data_range', ctypes.c_double), ('win', ctypes.c_int)]
+
+    def __init__(self, data_range=2.0, win=7):
+        super().__init__(ctypes.sizeof(EvalOpts), data_range, win)
 
 
 _lib = None
@@ -246,6 +260,10 @@ def load():
     lib.anr_profile_read_clock.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
                                            ctypes.POINTER(ctypes.c_double)]
     lib.anr_train_deterministic.argtypes = [ctypes.c_int]
+    lib.anr_eval_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_eval_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.anr_eval_frame.argtypes = [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(EvalOpts), P,
+                                   P, P, P, P, P, ctypes.c_size_t, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

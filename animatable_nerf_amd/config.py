@@ -81,6 +81,9 @@ def defaults():
         'ep_iter': 500, 'save_ep': 200, 'save_latest_ep': 5, 'eval_ep': 1000,
         'trained_model_dir': 'data/trained_model', 'record_dir': 'data/record', 'result_dir': 'data/result',
         'network_module': 'animatable_nerf_amd.network', 'renderer_module': 'animatable_nerf_amd.renderer',
+        # evaluator: SSIM data range (2.0 = what the reference's structural_similarity call resolves to for its
+        # float64 images), and the reference's comparison PNGs (opt-in: writing them synchronises every frame)
+        'eval_data_range': 2.0, 'eval_write_images': False,
     })
 
 

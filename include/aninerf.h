@@ -35,6 +35,7 @@
  *   anr_anim_step           lib/train/trainers/aninerf_animation_trainer.py:33-140 (forward + backward)
  *   anr_mc_count/anr_mc_emit  mcubes.marching_cubes(np.pad(cube, 10), cfg.mesh_th)
  *                             (aninerf_mesh_renderer.py:38-45; PyMCubes, third-party, not installed)
+ *   anr_eval_frame          lib/evaluators/if_nerf.py:15-74 Evaluator.evaluate (mse, psnr, ssim; A18)
  *
  * All float tensors are fp32, contiguous, row-major, with the reference's shapes (batch dim 1).
  */
@@ -539,6 +540,39 @@ int anr_mc_count(const float* vol, int X, int Y, int Z, int pad, double iso, int
                  size_t ws_bytes, void* stream);
 int anr_mc_emit(const float* vol, int X, int Y, int Z, int pad, double iso, double* vertices, int64_t* triangles,
                 void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- frame evaluator (lib/evaluators/if_nerf.py:15-74 Evaluator.evaluate: mse, psnr, ssim) -------------
+ * One frame on the device: rgb_pred / rgb_gt (n_rays,3) are the in-box rays in raster order of
+ * mask_at_box (H*W bytes, non-zero = set), as `img[mask_at_box] = rgb` assumes (if_nerf.py:26-29).
+ * ssim is skimage.metrics.structural_similarity(img_pred, img_gt, multichannel=True) on the float64 crop
+ * [y:y+h, x:x+w] (cv2.boundingRect of the mask) of the zero-filled (H,W,3) images: 7x7 uniform window,
+ * K1 0.01, K2 0.03, sample covariance, mean of S over the crop minus its 3-pixel border, then over the
+ * channels; all moments in float64. data_range defaults to 2.0: the reference passes none, and the
+ * scikit-image releases that accept its call (0.16-0.18) give a float64 image the dtype range (-1, 1).
+ * mse = sse / (3 n_rays) in float64, psnr = -10 log10(mse). Every reduction has a fixed order, so two
+ * calls on the same inputs write the same bits. A set pixel whose scanned index is >= n_rays reads
+ * nothing and counts as zero (status 3).
+ * out (ANR_EVAL_NOUT device doubles):
+ *   [0] sse  [1] 3*n_rays  [2] mse  [3] psnr  [4] ssim  [5] x [6] y [7] w [8] h (bounding rect)
+ *   [9] sum of rgb_gt
+ *   [10] status: 0 ok; 1 skipped (sum of rgb_gt == 0 or empty mask: the reference skips the frame);
+ *        2 crop narrower than the 7-pixel window (ssim = NaN, mse/psnr valid);
+ *        3 popcount(mask) != n_rays (nothing valid)
+ *   [11] 0
+ * Optional outputs (NULL: not written): img_pred / img_gt (H,W,3) f32, the zero-filled scatter;
+ * img8_pred / img8_gt (H,W,3) u8 RGB = rint(clip(255 v, 0, 255)), half to even.
+ * o == NULL means the defaults {data_range 2.0, win 7}; otherwise struct_size must be the size of the
+ * struct. Allocates nothing, does not synchronise, everything is enqueued on `stream`. */
+#define ANR_EVAL_NOUT 12
+typedef struct anr_eval_opts {
+  size_t struct_size;
+  double data_range; /* R of C1 = (0.01 R)^2, C2 = (0.03 R)^2 */
+  int win;           /* 7; others rejected */
+} anr_eval_opts;
+size_t anr_eval_workspace_bytes(int H, int W);
+int anr_eval_frame(const float* rgb_pred, const float* rgb_gt, int n_rays, const uint8_t* mask_at_box, int H, int W,
+                   const anr_eval_opts* o, double* out, float* img_pred, float* img_gt, uint8_t* img8_pred,
+                   uint8_t* img8_gt, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- measurement ----------------------------------------------------------------------
  * When enabled, anr_render_fwd records a hipEvent pair around the fused network kernel (k_mlp)
