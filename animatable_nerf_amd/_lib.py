@@ -34,7 +34,8 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_sdf_network_train_workspace_bytes', 'anr_sdf_network_train_fwd', 'anr_sdf_network_train_counts',
            'anr_sdf_network_train_rows', 'anr_sdf_network_train_bwd', 'anr_sdf_points_workspace_bytes', 'anr_sdf_points',
            'anr_sample_volume', 'anr_knn_blend_workspace_bytes', 'anr_knn_blend', 'anr_sdf_mesh_pose',
-           'anr_train_deterministic', 'anr_eval_workspace_bytes', 'anr_eval_frame', 'anr_last_error', 'anr_version')
+           'anr_train_deterministic', 'anr_eval_workspace_bytes', 'anr_eval_frame', 'anr_bw_volume_workspace_bytes',
+           'anr_bw_volume', 'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
 
@@ -132,6 +133,18 @@ class EvalOpts(ctypes.Structure):
 
     def __init__(self, data_range=2.0, win=7):
         super().__init__(ctypes.sizeof(EvalOpts), data_range, win)
+
+
+BWV_VERTEX, BWV_SURFACE = 0, 1  # anr_bwv_opts.mode
+BWV_DEFAULT, BWV_EXHAUSTIVE, BWV_PRUNED = 0, 1, 2  # anr_bwv_opts.exhaustive
+
+
+class BwvOpts(ctypes.Structure):
+    """anr_bwv_opts: struct_size is filled in by the constructor."""
+    _fields_ = [('struct_size', ctypes.c_uint32), ('mode', ctypes.c_int), ('exhaustive', ctypes.c_int)]
+
+    def __init__(self, mode=BWV_VERTEX, exhaustive=BWV_DEFAULT):
+        super().__init__(ctypes.sizeof(BwvOpts), mode, exhaustive)
 
 
 _lib = None
@@ -264,6 +277,10 @@ def load():
     lib.anr_eval_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.anr_eval_frame.argtypes = [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, ctypes.POINTER(EvalOpts), P,
                                    P, P, P, P, P, ctypes.c_size_t, P]
+    lib.anr_bw_volume_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_bw_volume_workspace_bytes.argtypes = [ctypes.c_int] * 5
+    lib.anr_bw_volume.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, D, ctypes.c_double, ctypes.c_int,
+                                  ctypes.c_int, ctypes.c_int, ctypes.POINTER(BwvOpts), P, P, P, ctypes.c_size_t, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

@@ -36,6 +36,8 @@
  *   anr_mc_count/anr_mc_emit  mcubes.marching_cubes(np.pad(cube, 10), cfg.mesh_th)
  *                             (aninerf_mesh_renderer.py:38-45; PyMCubes, third-party, not installed)
  *   anr_eval_frame          lib/evaluators/if_nerf.py:15-74 Evaluator.evaluate (mse, psnr, ssim; A18)
+ *   anr_bw_volume           tools/custom_dataset/prepare_blend_weights.py:156-211, 229-283 (the per-frame
+ *                             bweights/{i}.npy and the tbw.npy / bigpose_bw.npy volumes)
  *
  * All float tensors are fp32, contiguous, row-major, with the reference's shapes (batch dim 1).
  */
@@ -573,6 +575,34 @@ size_t anr_eval_workspace_bytes(int H, int W);
 int anr_eval_frame(const float* rgb_pred, const float* rgb_gt, int n_rays, const uint8_t* mask_at_box, int H, int W,
                    const anr_eval_opts* o, double* out, float* img_pred, float* img_gt, uint8_t* img8_pred,
                    uint8_t* img8_gt, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- blend-weight volumes (tools/custom_dataset/prepare_blend_weights.py:156-211, 229-283) --------------
+ * volume (X,Y,Z,nb+1) f32 over the 'ij' grid whose voxel (x, y, z) sits at origin + (x, y, z) * vsize
+ * (float64; origin is a HOST array of 3 doubles, the dims come from numpy's own arange on the host).
+ * mode 0 (vertex, bweights/{i}.npy): channels 0..nb-1 = skin (nv,nb) row of the closest vertex, bit for bit;
+ * channel nb = distance to it. mode 1 (surface, tbw.npy / bigpose_bw.npy): the closest point of the
+ * triangle mesh faces (nf,3) — its projection onto the triangle when that lies inside, else the closest
+ * of the three edge segments — channels 0..nb-1 = barycentric interpolation of the three vertices' rows
+ * there, channel nb = distance to it. The search runs in float32 ((dx*dx + dy*dy) + dz*dz fused, over
+ * the float32-rounded voxel position); among candidates with equal float32 squared distance the lowest
+ * vertex / face index wins, whatever the launch geometry. The winner's weights and distance are then
+ * recomputed in float64 and cast to float32 once. A zero-area triangle counts as its edges; no input
+ * geometry produces a NaN. index (X*Y*Z int32, optional) receives the winning vertex / face id.
+ * exhaustive: 0 = the library's default search, 1 = visit every primitive, 2 = skip cells of 64
+ * primitives by their bounding boxes; all three write the same bits.
+ * Face indices must lie in [0, nv): that is the caller's contract (the kernels clamp them, so a bad
+ * index reads a wrong vertex, never outside the array). o == NULL means {mode 0, exhaustive 0}.
+ * Allocates nothing, does not synchronise, everything is enqueued on `stream`; every element of volume
+ * (and index) is written. */
+typedef struct anr_bwv_opts {
+  uint32_t struct_size;
+  int mode;       /* 0 vertex, 1 surface */
+  int exhaustive; /* 0 default, 1 exhaustive, 2 pruned */
+} anr_bwv_opts;
+size_t anr_bw_volume_workspace_bytes(int nv, int nf, int X, int Y, int Z);
+int anr_bw_volume(const float* verts, int nv, const int32_t* faces, int nf, const float* skin, int nb,
+                  const double* origin, double vsize, int X, int Y, int Z, const anr_bwv_opts* o,
+                  float* volume, int32_t* index, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- measurement ----------------------------------------------------------------------
  * When enabled, anr_render_fwd records a hipEvent pair around the fused network kernel (k_mlp)
