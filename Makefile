@@ -13,10 +13,22 @@ DEPS := $(OBJS:.o=.d)
 LIB := animatable_nerf_amd/libaninerf_hip.so
 CXXFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Iinclude
 
-all: $(LIB)
+# test-only entries to the training GEMM launchers (tests/csrc/anr_testapi.hip): the library's own objects
+# plus the hooks, loaded by the GEMM kernel tests only
+TESTLIB := tests/libanr_testapi.so
+TESTOBJ := tests/csrc/anr_testapi.o
+DEPS += $(TESTOBJ:.o=.d)
+
+all: $(LIB) $(TESTLIB)
 
 $(SRC_DIR)/%.o: $(SRC_DIR)/%.hip
 	$(HIPCC) $(CXXFLAGS) -MMD -MP -c $< -o $@
+
+$(TESTOBJ): tests/csrc/anr_testapi.hip
+	$(HIPCC) $(CXXFLAGS) -MMD -MP -c $< -o $@
+
+$(TESTLIB): $(OBJS) $(TESTOBJ)
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@.tmp $(OBJS) $(TESTOBJ) && mv -f $@.tmp $@
 
 # the bf16x6 programs without SLP vectorisation: clang pairs the splits' scalar f32 subtractions into
 # v_pk_add_f32, which costs more issue cycles beside MFMAs than two v_sub_f32 (same-box A/B round 6:
@@ -33,7 +45,7 @@ resources: $(SRC_DIR)/anr_mlp.hip $(SRC_DIR)/anr_mlp_b16.hip
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_mlp_b16.hip -o /tmp/anr_mlp_b16_res.o -Rpass-analysis=kernel-resource-usage
 
 clean:
-	rm -f $(OBJS) $(DEPS) $(LIB)
+	rm -f $(OBJS) $(DEPS) $(LIB) $(TESTOBJ) $(TESTLIB)
 
 .PHONY: all clean resources
 
