@@ -35,7 +35,8 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_sdf_network_train_rows', 'anr_sdf_network_train_bwd', 'anr_sdf_points_workspace_bytes', 'anr_sdf_points',
            'anr_sample_volume', 'anr_knn_blend_workspace_bytes', 'anr_knn_blend', 'anr_sdf_mesh_pose',
            'anr_train_deterministic', 'anr_eval_workspace_bytes', 'anr_eval_frame', 'anr_bw_volume_workspace_bytes',
-           'anr_bw_volume', 'anr_last_error', 'anr_version')
+           'anr_bw_volume', 'anr_mesh_cc_workspace_bytes', 'anr_mesh_cc_count', 'anr_mesh_cc_emit', 'anr_last_error',
+           'anr_version')
 
 c_float_p = ctypes.c_void_p
 
@@ -134,6 +135,11 @@ class EvalOpts(ctypes.Structure):
     def __init__(self, data_range=2.0, win=7):
         super().__init__(ctypes.sizeof(EvalOpts), data_range, win)
 
+
+MESHCC_NCOUNT = 6  # ANR_MESHCC_NCOUNT: int32 counts of anr_mesh_cc_count
+# indices into the counts, and the status values
+MESHCC_V, MESHCC_T, MESHCC_NCOMP, MESHCC_NWATERTIGHT, MESHCC_KEPT, MESHCC_STATUS = range(6)
+MESHCC_OK, MESHCC_NONE_WATERTIGHT, MESHCC_BAD_INDEX = 0, 1, 2
 
 BWV_VERTEX, BWV_SURFACE = 0, 1  # anr_bwv_opts.mode
 BWV_DEFAULT, BWV_EXHAUSTIVE, BWV_PRUNED = 0, 1, 2  # anr_bwv_opts.exhaustive
@@ -281,6 +287,10 @@ def load():
     lib.anr_bw_volume_workspace_bytes.argtypes = [ctypes.c_int] * 5
     lib.anr_bw_volume.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, D, ctypes.c_double, ctypes.c_int,
                                   ctypes.c_int, ctypes.c_int, ctypes.POINTER(BwvOpts), P, P, P, ctypes.c_size_t, P]
+    lib.anr_mesh_cc_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_mesh_cc_workspace_bytes.argtypes = [ctypes.c_long, ctypes.c_long]
+    lib.anr_mesh_cc_count.argtypes = [P, ctypes.c_long, ctypes.c_long, P, P, P, ctypes.c_size_t, P]
+    lib.anr_mesh_cc_emit.argtypes = [P, P, ctypes.c_long, ctypes.c_long, P, P, P, ctypes.c_size_t, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

@@ -11,7 +11,10 @@
 * the volume ``cube[inside] = alpha`` (:38-41) is assembled on the device;
 * ``marching_cubes``: ``mcubes.marching_cubes(np.pad(cube, 10), cfg.mesh_th)`` (:43-45) through
   ``anr_mc_count`` / ``anr_mc_emit`` (padding virtual), then ``(v - 10) * voxel_size[0] +
-  wbounds[0]`` (:46-47).
+  wbounds[0]`` (:46-47);
+* with the cfg key ``mesh_largest_component`` (default off: the reference returns every piece) the
+  largest watertight component of that mesh alone, ``largest_component_device`` (``anr_mesh_cc_count``
+  / ``anr_mesh_cc_emit``), before the vertex transform.
 
 PyMCubes is not installed here, so its triangulation cannot be pinned: the vertex set (one vertex
 per crossing grid edge, linear interpolation) is table-independent; the triangles follow the case
@@ -59,6 +62,42 @@ def marching_cubes(cube, iso, pad=MC_PAD):
         _lib.check(lib.anr_mc_emit(_lib.ptr(vol), X, Y, Z, pad, float(iso), _lib.ptr(verts), _lib.ptr(tris),
                                    _lib.ptr(ws), nbytes, st), 'anr_mc_emit')
     return verts, tris
+
+
+def largest_component_device(vertices, triangles, return_labels=False):
+    """The host ``renderer_sdf_mesh.largest_component`` on the device (``anr_mesh_cc_count`` /
+    ``anr_mesh_cc_emit``): ``vertices`` (V,3) float64 and ``triangles`` (T,3) int64 CUDA tensors ->
+    the largest watertight component (vertices (V',3), triangles (T',3)) as device tensors, the
+    inputs' values when no component is watertight; with ``return_labels`` also every input face's
+    component label (its component's lowest face index), (T,) int32. One host read of the counts
+    sizes the outputs. A face index outside [0, V) raises ValueError."""
+    lib = _lib.load()
+    dev = vertices.device
+    if vertices.dtype != torch.float64 or triangles.dtype != torch.int64:
+        raise TypeError('largest_component_device takes float64 vertices and int64 triangles')
+    if not vertices.is_cuda or triangles.device != dev:
+        raise ValueError('largest_component_device takes tensors of one CUDA device (numpy: largest_component)')
+    v = vertices.reshape(-1, 3).contiguous()
+    t = triangles.reshape(-1, 3).contiguous()
+    nv, nt = int(v.shape[0]), int(t.shape[0])
+    nbytes = lib.anr_mesh_cc_workspace_bytes(nv, nt)
+    if nbytes == 0:
+        raise ValueError(f'largest_component_device: mesh too large ({nv} vertices, {nt} triangles)')
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(_lib.MESHCC_NCOUNT, dtype=torch.int32, device=dev)
+    labels = torch.empty(nt, dtype=torch.int32, device=dev) if return_labels else None
+    st = _lib.stream_ptr(dev)
+    _lib.check(lib.anr_mesh_cc_count(_lib.ptr(t), nt, nv, _lib.ptr(counts), _lib.ptr(labels), _lib.ptr(ws), nbytes, st),
+               'anr_mesh_cc_count')
+    c = [int(x) for x in counts.cpu()]
+    if c[_lib.MESHCC_STATUS] == _lib.MESHCC_BAD_INDEX:
+        raise ValueError(f'largest_component_device: a triangle index is outside [0, {nv})')
+    kv = torch.empty((c[_lib.MESHCC_V], 3), dtype=torch.float64, device=dev)
+    kt = torch.empty((c[_lib.MESHCC_T], 3), dtype=torch.int64, device=dev)
+    if kv.shape[0] > 0 or kt.shape[0] > 0:
+        _lib.check(lib.anr_mesh_cc_emit(_lib.ptr(v), _lib.ptr(t), nt, nv, _lib.ptr(kv), _lib.ptr(kt), _lib.ptr(ws),
+                                        nbytes, st), 'anr_mesh_cc_emit')
+    return (kv, kt, labels) if return_labels else (kv, kt)
 
 
 class Renderer(_renderer.Renderer):
@@ -124,6 +163,10 @@ class Renderer(_renderer.Renderer):
         with torch.no_grad():
             cube = self.alpha_volume(batch)
             verts, tris = marching_cubes(cube, float(self.cfg.get('mesh_th', 5.0)), MC_PAD)
+            # opt-in (the reference left its connected_component_labels commented out, :46-55): drop the
+            # floaters, keeping the largest watertight component
+            if self.cfg.get('mesh_largest_component', False):
+                verts, tris = largest_component_device(verts, tris)
         voxel = self.cfg.get('voxel_size', [0.005, 0.005, 0.005])
         wmin = batch['wbounds'][0, 0].detach().cpu().numpy()
         vertices = (verts.cpu().numpy() - MC_PAD) * voxel[0]

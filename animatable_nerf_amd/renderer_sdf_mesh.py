@@ -10,10 +10,11 @@
 * ``tpose_human.sdf_network`` over the inside points (:64-68): ``anr_sdf_points`` (exact fp32);
 * ``cube = -sdf`` (10 outside), padded by 10 with -10 (:70-75), marching cubes at 0: the device marching
   cubes of the aninerf mesh path (``renderer_mesh.marching_cubes``) over the padded cube;
-* ``trimesh.Trimesh(...).split()`` and the largest component (:76-77): ``largest_component`` (host graph
-  pass over the triangle list: faces joined through shared edges, watertight components only, the
-  vertices of the kept component in their original order) — trimesh is not installed here, so this
-  step is parity unpinned;
+* ``trimesh.Trimesh(...).split()`` and the largest component (:76-77): ``largest_component_device``
+  (``anr_mesh_cc_count`` / ``anr_mesh_cc_emit``: faces joined through shared edges, watertight components
+  only, the vertices of the kept component in their original order), bit-equal to the host
+  ``largest_component`` below, which stays as its yardstick and as the path for numpy inputs — trimesh
+  is not installed here, so this step is parity unpinned;
 * vertices to the big-pose frame (:78-79); their blend weights (:82-84, ``anr_knn_blend``); the
   deformation ``-normal * sdf`` of ``gradient_of_deformed_sdf`` (:88-92, ``anr_sdf_points``); big pose ->
   T pose -> pose -> world (:96-101, ``anr_sdf_mesh_pose``).
@@ -23,7 +24,7 @@ import torch
 
 from . import _lib
 from . import config as _config
-from .renderer_mesh import marching_cubes
+from .renderer_mesh import largest_component_device, marching_cubes
 
 MC_PAD = 10      # sdf_mesh_renderer.py:73
 NORM_TH = 0.1    # :59
@@ -118,7 +119,8 @@ class Renderer:
         with torch.no_grad():
             cube = self.sdf_volume(batch)
             verts, tris = marching_cubes(cube, 0.0, 0)
-            vertices, triangles = largest_component(verts.cpu().numpy(), tris.cpu().numpy())
+            verts, tris = largest_component_device(verts, tris)  # only the kept mesh leaves the device
+            vertices, triangles = verts.cpu().numpy(), tris.cpu().numpy()
             voxel = self.cfg.get('voxel_size', [0.005, 0.005, 0.005])
             vertices = (vertices - MC_PAD) * voxel[0]
             vertices = vertices + batch['tbounds'][0, 0].detach().cpu().numpy()

@@ -36,6 +36,8 @@
  *   anr_mc_count/anr_mc_emit  mcubes.marching_cubes(np.pad(cube, 10), cfg.mesh_th)
  *                             (aninerf_mesh_renderer.py:38-45; PyMCubes, third-party, not installed)
  *   anr_eval_frame          lib/evaluators/if_nerf.py:15-74 Evaluator.evaluate (mse, psnr, ssim; A18)
+ *   anr_mesh_cc_count/anr_mesh_cc_emit  max(trimesh.Trimesh(v, t).split(), key=lambda m: len(m.vertices))
+ *                             (sdf_mesh_renderer.py:77-78; trimesh, third-party, not installed)
  *   anr_bw_volume           tools/custom_dataset/prepare_blend_weights.py:156-211, 229-283 (the per-frame
  *                             bweights/{i}.npy and the tbw.npy / bigpose_bw.npy volumes)
  *
@@ -542,6 +544,29 @@ int anr_mc_count(const float* vol, int X, int Y, int Z, int pad, double iso, int
                  size_t ws_bytes, void* stream);
 int anr_mc_emit(const float* vol, int X, int Y, int Z, int pad, double iso, double* vertices, int64_t* triangles,
                 void* workspace, size_t ws_bytes, void* stream);
+/* The largest watertight component of a triangle mesh (vertices (nv,3) f64, triangles (nt,3) int64, both on
+ * the device), with the semantics of the host renderer_sdf_mesh.largest_component for every input whose
+ * indices lie in [0, nv): faces are joined through shared undirected edges only; an edge's multiplicity is
+ * the number of face sides carrying its vertex pair (all three sides of every face count, duplicate and
+ * degenerate faces included); a component's label is its lowest face index; a component is watertight when
+ * every one of its edges has multiplicity 2; the watertight component with the most distinct vertices is
+ * kept, the lowest label on a tie. Output faces keep their input order, output vertices are the sorted
+ * distinct vertex ids of the kept faces, and the faces are renumbered to those positions.
+ * anr_mesh_cc_count writes device int32 counts {V', T', n_components, n_watertight, kept_label, status} and,
+ * when labels != NULL, each face's component label. status 0: ok. status 1: no watertight component (or
+ * nt == 0): kept_label -1, V' = nv, T' = nt and anr_mesh_cc_emit copies the inputs. status 2: an index was
+ * outside [0, nv): V' = T' = 0, no index is dereferenced, labels are -1 and anr_mesh_cc_emit writes nothing.
+ * anr_mesh_cc_emit (same triangles / workspace, after the caller sized the outputs) writes out_vertices (V',3)
+ * and out_triangles (T',3). No allocation, no host synchronisation, integer reductions only (two calls on one
+ * input write the same bits). 3 nt >= 2^31, nv + 1 >= 2^31, negative counts, NULL pointers (triangles may be
+ * NULL when nt == 0, vertices when nv == 0) and a short workspace are rejected before any HIP call;
+ * anr_mesh_cc_workspace_bytes returns 0 for such counts. */
+#define ANR_MESHCC_NCOUNT 6
+size_t anr_mesh_cc_workspace_bytes(long nv, long nt);
+int anr_mesh_cc_count(const int64_t* triangles, long nt, long nv, int32_t* counts, int32_t* labels, void* workspace,
+                      size_t ws_bytes, void* stream);
+int anr_mesh_cc_emit(const double* vertices, const int64_t* triangles, long nt, long nv, double* out_vertices,
+                     int64_t* out_triangles, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- frame evaluator (lib/evaluators/if_nerf.py:15-74 Evaluator.evaluate: mse, psnr, ssim) -------------
  * One frame on the device: rgb_pred / rgb_gt (n_rays,3) are the in-box rays in raster order of
