@@ -35,8 +35,9 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_sdf_network_train_rows', 'anr_sdf_network_train_bwd', 'anr_sdf_points_workspace_bytes', 'anr_sdf_points',
            'anr_sample_volume', 'anr_knn_blend_workspace_bytes', 'anr_knn_blend', 'anr_sdf_mesh_pose',
            'anr_train_deterministic', 'anr_eval_workspace_bytes', 'anr_eval_frame', 'anr_bw_volume_workspace_bytes',
-           'anr_bw_volume', 'anr_mesh_cc_workspace_bytes', 'anr_mesh_cc_count', 'anr_mesh_cc_emit', 'anr_last_error',
-           'anr_version')
+           'anr_bw_volume', 'anr_mesh_cc_workspace_bytes', 'anr_mesh_cc_count', 'anr_mesh_cc_emit',
+           'anr_mesh_dist_workspace_bytes', 'anr_mesh_sample', 'anr_mesh_point_dist', 'anr_mesh_metrics', 'anr_mesh_order',
+           'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
 
@@ -151,6 +152,23 @@ class BwvOpts(ctypes.Structure):
 
     def __init__(self, mode=BWV_VERTEX, exhaustive=BWV_DEFAULT):
         super().__init__(ctypes.sizeof(BwvOpts), mode, exhaustive)
+
+
+MESHM_NOUT = 8  # ANR_MESHM_NOUT: doubles of one anr_mesh_metrics row
+MESHM_CHAMFER, MESHM_P2S, MESHM_SRC_TGT, MESHM_TGT_SRC, MESHM_STATUS = range(5)
+MESHM_BAD_SOURCE, MESHM_BAD_TARGET = 1, 2  # bits of row[MESHM_STATUS]
+MESH_MAX_FACES, MESH_MAX_POINTS = 1 << 26, 1 << 24
+# anr_meshdist_opts.exhaustive: BWV_DEFAULT, BWV_EXHAUSTIVE, BWV_PRUNED (two levels of boxes) and
+MESHDIST_PRUNED_CELLS = 3  # pruned by the cell boxes alone
+
+
+class MeshDistOpts(ctypes.Structure):
+    """anr_meshdist_opts: struct_size is filled in by the constructor; 0 samples mean the reference's counts."""
+    _fields_ = [('struct_size', ctypes.c_uint32), ('exhaustive', ctypes.c_int), ('n_chamfer', ctypes.c_int),
+                ('n_p2s', ctypes.c_int)]
+
+    def __init__(self, exhaustive=BWV_DEFAULT, n_chamfer=0, n_p2s=0):
+        super().__init__(ctypes.sizeof(MeshDistOpts), exhaustive, n_chamfer, n_p2s)
 
 
 _lib = None
@@ -291,6 +309,15 @@ def load():
     lib.anr_mesh_cc_workspace_bytes.argtypes = [ctypes.c_long, ctypes.c_long]
     lib.anr_mesh_cc_count.argtypes = [P, ctypes.c_long, ctypes.c_long, P, P, P, ctypes.c_size_t, P]
     lib.anr_mesh_cc_emit.argtypes = [P, P, ctypes.c_long, ctypes.c_long, P, P, P, ctypes.c_size_t, P]
+    lib.anr_mesh_dist_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_mesh_dist_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+    MO = ctypes.POINTER(MeshDistOpts)
+    lib.anr_mesh_sample.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, P, P, P, P, ctypes.c_size_t, P]
+    lib.anr_mesh_point_dist.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, MO, P, P, P, P,
+                                        ctypes.c_size_t, P]
+    lib.anr_mesh_order.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, P, ctypes.c_size_t, P]
+    lib.anr_mesh_metrics.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, P, MO, P, P,
+                                     ctypes.c_size_t, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

@@ -84,6 +84,8 @@ def defaults():
         # evaluator: SSIM data range (2.0 = what the reference's structural_similarity call resolves to for its
         # float64 images), and the reference's comparison PNGs (opt-in: writing them synchronises every frame)
         'eval_data_range': 2.0, 'eval_write_images': False,
+        # mesh evaluator: the reference's posed_mesh/{frame:04d}.ply (opt-in: the copy to the host synchronises)
+        'eval_write_meshes': False,
     })
 
 

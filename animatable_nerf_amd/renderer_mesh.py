@@ -173,3 +173,16 @@ class Renderer(_renderer.Renderer):
         vertices = vertices + wmin
         triangles = tris.cpu().numpy()
         return {'vertex': vertices, 'posed_vertex': vertices, 'triangle': triangles}
+
+    def render_device(self, batch):
+        """``render`` with the mesh left on the device: the same three keys as tensors (vertices (V,3)
+        float64, triangles (T,3) int64), for ``evaluator_mesh.Evaluator.evaluate``."""
+        with torch.no_grad():
+            cube = self.alpha_volume(batch)
+            verts, tris = marching_cubes(cube, float(self.cfg.get('mesh_th', 5.0)), MC_PAD)
+            if self.cfg.get('mesh_largest_component', False):
+                verts, tris = largest_component_device(verts, tris)
+            voxel = self.cfg.get('voxel_size', [0.005, 0.005, 0.005])
+            vertices = (verts - MC_PAD) * voxel[0]
+            vertices = vertices + batch['wbounds'][0, 0].detach().to(device=verts.device, dtype=verts.dtype)
+        return {'vertex': vertices, 'posed_vertex': vertices, 'triangle': tris}

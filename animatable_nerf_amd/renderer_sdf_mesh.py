@@ -126,3 +126,17 @@ class Renderer:
             vertices = vertices + batch['tbounds'][0, 0].detach().cpu().numpy()
             posed = self.posed_vertices(vertices, batch).cpu().numpy()
         return {'vertex': vertices, 'posed_vertex': posed, 'triangle': triangles}
+
+    def render_device(self, batch):
+        """``render`` with the mesh left on the device: the same three keys as tensors (vertex (V,3) float64,
+        posed_vertex (V,3) float32, triangle (T,3) int64), equal to ``render``'s arrays. With
+        ``evaluator_mesh.Evaluator.evaluate`` the loop render -> evaluate keeps the mesh in HBM."""
+        with torch.no_grad():
+            cube = self.sdf_volume(batch)
+            verts, tris = marching_cubes(cube, 0.0, 0)
+            verts, tris = largest_component_device(verts, tris)
+            voxel = self.cfg.get('voxel_size', [0.005, 0.005, 0.005])
+            vertices = (verts - MC_PAD) * voxel[0]
+            vertices = vertices + batch['tbounds'][0, 0].detach().to(device=verts.device, dtype=verts.dtype)
+            posed = self.posed_vertices(vertices, batch)
+        return {'vertex': vertices, 'posed_vertex': posed, 'triangle': tris}

@@ -40,6 +40,12 @@
  *                             (sdf_mesh_renderer.py:77-78; trimesh, third-party, not installed)
  *   anr_bw_volume           tools/custom_dataset/prepare_blend_weights.py:156-211, 229-283 (the per-frame
  *                             bweights/{i}.npy and the tbw.npy / bigpose_bw.npy volumes)
+ *   anr_mesh_sample         trimesh.sample.sample_surface (lib/evaluators/mesh_evaluator.py:103-107, 126-127;
+ *                             trimesh, third-party, not installed)
+ *   anr_mesh_point_dist     trimesh.proximity.closest_point (mesh_evaluator.py:109-112, 129-130)
+ *   anr_mesh_metrics        MeshEvaluator.get_chamfer_dist + get_surface_dist of one frame (:100-136)
+ *   anr_mesh_order          the linear-time Morton ordering of the faces that the search is built on
+ *   anr_mesh_dist_workspace_bytes  the workspace of the four above
  *
  * All float tensors are fp32, contiguous, row-major, with the reference's shapes (batch dim 1).
  */
@@ -628,6 +634,56 @@ size_t anr_bw_volume_workspace_bytes(int nv, int nf, int X, int Y, int Z);
 int anr_bw_volume(const float* verts, int nv, const int32_t* faces, int nf, const float* skin, int nb,
                   const double* origin, double vsize, int X, int Y, int Z, const anr_bwv_opts* o,
                   float* volume, int32_t* index, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- mesh evaluator (lib/evaluators/mesh_evaluator.py:19-136: Chamfer and point-to-surface) -------------
+ * Meshes are vertices (nv,3) f32 and faces (nf,3) int32 on the device, as for anr_bw_volume; a face index
+ * outside [0, nv) is clamped before any read. Limits: nf <= 2^26, points per call <= 2^24.
+ * anr_mesh_sample restates trimesh.sample.sample_surface(mesh, n) (trimesh is third-party and not installed:
+ *   parity unpinned). area = 0.5 |e0 x e1| in float64 (e0 = b - a, e1 = c - a), cum = its inclusive float64
+ *   prefix sum; sample i takes u[i] = (u0, u1, u2) in [0, 1) (u (n,3) f64, device): face k =
+ *   searchsorted(cum, u0 cum[-1], side='left'); if u1 + u2 > 1 both become |u - 1|; point = a_k + (e0 u1 +
+ *   e1 u2) in float64 without contraction. points (n,3) f64, face (n) int32. status (one device int32): 0, or
+ *   1 when nf <= 0 or the total area is zero or not finite; then nothing is drawn (points 0, face -1).
+ * anr_mesh_point_dist: for each of n points (n,3) f64 the closest face and the distance to it (dist (n) f64,
+ *   face (n) int32 or NULL). The search is anr_bw_volume's surface search over a point list: float32 records
+ *   and queries taken about the centre of the mesh's box (subtracted in float64, so a mesh metres from the
+ *   origin loses nothing), faces and queries in 30-bit Morton order (a linear-time radix sort), cells of 64
+ *   faces pruned by their boxes, groups of 64 cells by a box of their own; the winner is the lowest (float32
+ *   d^2, face index), then its distance is recomputed in float64 from the original vertices. exhaustive: 0 = the
+ *   library's default search, 1 = visit every face, 2 = both levels of boxes, 3 = the cell boxes alone; all
+ *   write the same bits, and the result of a point does not depend on the other points. mean (one device double, or NULL)
+ *   receives the mean distance with a NaN counted as 0 (mesh_evaluator.py:114-115), summed in a fixed order.
+ * anr_mesh_metrics: one frame. u ((2 n_chamfer + n_p2s),3) f64 in the reference's draw order: source Chamfer,
+ *   target Chamfer, source P2S. out (ANR_MESHM_NOUT device doubles):
+ *   [0] chamfer = (src_tgt + tgt_src) / 2   [1] p2s = mean distance of the n_p2s source samples to the target
+ *   [2] src_tgt, [3] tgt_src: the means over the n_chamfer samples   [4] status: bit 0 the source, bit 1 the
+ *   target has no face or no finite positive area (then [0..3] are NaN)   [5..7] 0
+ * o == NULL means {exhaustive 0, n_chamfer 1000, n_p2s 10000}; a zero n_chamfer / n_p2s selects that default.
+ * One workspace serves all three: anr_mesh_dist_workspace_bytes(nf, n_pts) with nf the larger face count and
+ * n_pts the points of the call (2 n_chamfer + n_p2s for anr_mesh_metrics); it returns 0 for sizes outside the
+ * limits. NULL pointers, bad sizes and a short workspace are rejected before any HIP call. Allocates nothing,
+ * does not synchronise, everything is enqueued on `stream`. */
+#define ANR_MESHM_NOUT 8
+typedef struct anr_meshdist_opts {
+  uint32_t struct_size;
+  int exhaustive; /* 0 default, 1 exhaustive, 2 pruned by two levels of boxes, 3 pruned by the cell boxes alone */
+  int n_chamfer;  /* 0: 1000 */
+  int n_p2s;      /* 0: 10000 */
+} anr_meshdist_opts;
+size_t anr_mesh_dist_workspace_bytes(int nf, int n_pts);
+int anr_mesh_sample(const float* verts, int nv, const int32_t* faces, int nf, const double* u, int n, double* points,
+                    int32_t* face, int32_t* status, void* workspace, size_t ws_bytes, void* stream);
+int anr_mesh_point_dist(const float* verts, int nv, const int32_t* faces, int nf, const double* points, int n,
+                        const anr_meshdist_opts* o, double* dist, int32_t* face, double* mean, void* workspace,
+                        size_t ws_bytes, void* stream);
+/* The ordering alone (tools/mesh_eval_ab.py times it; the search does not depend on it): perm (nf) int32 = the
+ * faces sorted by (30-bit Morton code of the centroid over the mesh's box, face index). Workspace:
+ * anr_mesh_dist_workspace_bytes(nf, 1). */
+int anr_mesh_order(const float* verts, int nv, const int32_t* faces, int nf, int32_t* perm, void* workspace,
+                   size_t ws_bytes, void* stream);
+int anr_mesh_metrics(const float* src_verts, int src_nv, const int32_t* src_faces, int src_nf, const float* tgt_verts,
+                     int tgt_nv, const int32_t* tgt_faces, int tgt_nf, const double* u, const anr_meshdist_opts* o,
+                     double* out, void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- measurement ----------------------------------------------------------------------
  * When enabled, anr_render_fwd records a hipEvent pair around the fused network kernel (k_mlp)
