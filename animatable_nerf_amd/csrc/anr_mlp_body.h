@@ -50,6 +50,17 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #ifndef ANR_FAST_MATH
 #define ANR_FAST_MATH 1
 #endif
+// exact fp32 layers: 4-out-block chunks of A fragments per k-step held in registers (mlp_slice_max)
+#define ANR_F32_WMAX 5
+// exact fp32 layers: carry the one-k-step-ahead fragment reads across layer and tile boundaries
+// (0: every layer reads its first k-step's fragments itself, after its bias reads)
+#ifndef ANR_F32_XLAYER
+#define ANR_F32_XLAYER 1
+#endif
+// exact fp32 layers: spread a refill's LDS-DMA pieces over the k-steps after mid() (as ANR_DMA_SPREAD)
+#ifndef ANR_F32_DMA_SPREAD
+#define ANR_F32_DMA_SPREAD 1
+#endif
 
 // The per-tile layer program, variant V:
 //   V = 0 (render): entries 0..8 the pose-space BW MLP, 9..17 the T-pose BW MLP (layers 0..8
@@ -203,6 +214,37 @@ __host__ __device__ constexpr int prog_later_loads(int e, int q) {
   return n;
 }
 
+// Exact fp32 layers (mode 0), the fragment stream. Count the k-steps of the cyclic program 0, 1, 2, ...;
+// k-step n lies in slice n / ANR_KSLICE (an entry's k-steps are whole slices). The A fragments of
+// k-step n + 1 are read during k-step n, chunk cc right after the MFMAs that consumed chunk cc of
+// k-step n, into the same registers (Pipe::w), and waited for before the MFMAs of k-step n + 1.
+//  * Certified: the read targets the slice of k-step n, which the wave is consuming, or the next one
+//    from that slice's last k-step: after its mid() (k-step F32_MID of the slice), whose wait and
+//    barrier make every wave's pieces of the next slice visible.
+//  * Not being refilled: mid() of slice Q refills the slot of slice Q - 1. The last reads of that slot
+//    fetch the last k-step of Q - 1 and are waited for before its MFMAs, which every wave has issued
+//    before it arrives at the barrier in mid() of Q (the reads in flight there target slice Q itself);
+//    the refill's pieces follow that barrier, at once or spread over the slice's later k-steps
+//    (ANR_F32_DMA_SPREAD). The slot of Q + 1, read from k-step ANR_KSLICE - 1 of Q, is refilled by mid() of
+//    Q + 2, after k-step 0 of Q + 1 consumed those fragments; with a ring of >= 3 slots it is also not
+//    the slot mid() of Q has just started to fill (that of Q - 1, i.e. Q + nbuf - 1).
+// f32_stream_ok states these rules over one pass of the program, the wrap to entry 0 included.
+template <int V>
+__host__ __device__ constexpr bool f32_stream_ok() {
+  constexpr int F32_MID = ANR_KSLICE / 2 - 1;  // mid() follows this k-step's MFMAs and fragment reads
+  int n = 0;
+  for (int e = 0; e < prog_len<V>(); ++e) {
+    if (layer_ksteps(prog_layer<V>(e)) % ANR_KSLICE != 0) return false;  // slices do not straddle entries
+    if (layer_chunks(prog_layer<V>(e)) > ANR_F32_WMAX) return false;
+    n += layer_ksteps(prog_layer<V>(e));
+  }
+  for (int i = 0; i < n; ++i) {  // the reads issued during k-step i fetch k-step i + 1 (n: entry 0 again)
+    const int s = i / ANR_KSLICE, s1 = (i + 1) / ANR_KSLICE;
+    if (s1 != s && !(s1 == s + 1 && i % ANR_KSLICE > F32_MID)) return false;  // certified
+    if (i + 1 >= (s1 + 1) * ANR_KSLICE + F32_MID) return false;  // consumed before the slot's refill
+  }
+  return mlp_nbuf<false>() >= 3;
+}
 // s_waitcnt with only vmcnt constrained (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt_hi[15:14])
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
@@ -220,6 +262,9 @@ struct Pipe {
   int lane;
   int pose_woff;  // added to slices of the pose-space BW pass (novel_pose_bw weights)
   int pend;       // ring slot of the refill whose pieces are being spread (ANR_DMA_SPREAD)
+  // exact fp32 layers: the A fragments of the k-step consumed next, chunk by chunk. They live across
+  // k-steps, slices, entries and tiles (f32_stream_ok); the other kernels never touch them.
+  f32x4 w[ANR_F32_WMAX];
 
   // issue the HBM/L2 -> LDS copy of `kb` KiB at byte `off` of the packed image into ring slot `buf`;
   // every wave issues exactly `loads` 1-KiB pieces (pieces past the end repeat the last one: same
@@ -306,6 +351,22 @@ struct Pipe {
     if constexpr (I0 < i1) stage(off + (prog_pose(EE) ? pose_woff : 0), prog_slice_kb<B16, V>(EE, QQ), i1, pend, I0);
   }
   __device__ __forceinline__ void leave() { cur = cur + 1 >= nbuf ? 0 : cur + 1; }
+  // exact fp32 layers: chunks [C0, C1) of the fragments of k-step KS of a slice whose k-steps hold C
+  // chunks each, from the current ring slot or (NEXT) from the one after it
+  template <int C, int KS, int C0, int C1, bool NEXT>
+  __device__ __forceinline__ void read_w() {
+    const unsigned char* src = lds + (NEXT ? (cur + 1 >= nbuf ? 0 : cur + 1) : cur) * smax;
+    static_for<C0, C1>([&](auto c) {
+      constexpr int cc = decltype(c)::value;
+      w[cc] = *(const f32x4*)(src + ((KS * C + cc) * 64 + lane) * 16);
+    });
+  }
+  // after start(): the fragments of the program's first k-step
+  template <int V>
+  __device__ __forceinline__ void prime_f32() {
+    constexpr int C = layer_chunks(prog_layer<V>(0));
+    read_w<C, 0, 0, C, false>();
+  }
 };
 
 // x -> hi = bf16(x), lo = bf16(x - hi)   (RNE both)
@@ -909,19 +970,27 @@ __device__ __forceinline__ void layer(Pipe& p, const f32x4 (&in)[NIN], const flo
       p.leave();
     }
   } else {
+    // exact fp32 (mode 0): per k-step of 4 one B value per lane and one MFMA per out-block; the A
+    // fragments (C chunks of 4 out-blocks) are in p.w, read one k-step ahead (f32_stream_ok): chunk
+    // cc of the next k-step goes into w[cc] as soon as this k-step's MFMAs of chunk cc are issued,
+    // pinned there, so that a read has the other chunks' MFMAs to land behind and no k-step waits for
+    // its fragments. The last k-step reads the first fragments of the next entry (for the last entry:
+    // of entry 0, the next tile's), which the slice stream holds in the next ring slot like any slice.
+    static_assert(f32_stream_ok<V>(), "fp32 fragment stream reads an uncertified slice");
     constexpr int C = layer_chunks(L);
     constexpr int K = layer_ksteps(L);
     constexpr int K0 = D.seg[0].ksteps;
-    const unsigned char* buf = nullptr;
+    constexpr int CN = layer_chunks(prog_layer<V>((E + 1) % prog_len<V>()));  // chunks of the next entry
     static_for<0, K>([&](auto t) {
       constexpr int tt = decltype(t)::value;
-      if constexpr (tt % ANR_KSLICE == 0) buf = p.template enter<B16, V, E, tt / ANR_KSLICE>();
-      if constexpr (tt == 0) init_bias();
-      f32x4 w[C];
-      static_for<0, C>([&](auto c) {
-        constexpr int cc = decltype(c)::value;
-        w[cc] = *(const f32x4*)(buf + (((tt % ANR_KSLICE) * C + cc) * 64 + lane) * 16);
-      });
+      constexpr int ks = tt % ANR_KSLICE;
+      constexpr int Q = tt / ANR_KSLICE;
+      constexpr int MIDK = ANR_KSLICE / 2 - 1;
+      if constexpr (ks == 0) p.template enter<B16, V, E, Q>();
+      if constexpr (tt == 0) {
+        init_bias();
+        if constexpr (!ANR_F32_XLAYER) p.template read_w<C, 0, 0, C, false>();
+      }
       constexpr int seg = tt < K0 ? 0 : 1;
       constexpr int ts = tt < K0 ? tt : tt - K0;
       constexpr int kind = D.seg[seg].kind;
@@ -929,12 +998,33 @@ __device__ __forceinline__ void layer(Pipe& p, const f32x4 (&in)[NIN], const flo
       if constexpr (kind == SRC_EMB) b = emb[ts];
       else if constexpr (kind == SRC_VEMB) b = vemb[ts];
       else b = in[ts >> 2][ts & 3];
-      static_for<0, D.ob>([&](auto ob) {
-        constexpr int o = decltype(ob)::value;
-        out[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[o >> 2][o & 3], b, out[o], 0, 0, 0);
+      // the k-step after this one: in this slice, in the next slice, or the next entry's first
+      constexpr bool LAST = tt == K - 1;
+      constexpr int NC = !LAST ? C : ANR_F32_XLAYER ? CN : 0;
+      constexpr int NCC = LAST ? CN : C;  // chunks per k-step of the slice read from
+      constexpr bool NEXT = ks == ANR_KSLICE - 1;
+      constexpr int NKS = NEXT ? 0 : ks + 1;
+      static_for<0, C>([&](auto c) {
+        constexpr int cc = decltype(c)::value;
+        static_for<4 * cc, (4 * cc + 4 < D.ob ? 4 * cc + 4 : D.ob)>([&](auto ob) {
+          constexpr int o = decltype(ob)::value;
+          out[o] = __builtin_amdgcn_mfma_f32_16x16x4f32(p.w[cc][o & 3], b, out[o], 0, 0, 0);
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (cc < NC) p.template read_w<NCC, NKS, cc, cc + 1, NEXT>();
+        // the refill picked by mid(): one 1-KiB piece per wave and k-step of the slice's second half,
+        // not a burst of all of them behind the barrier, where the eight waves queue theirs at the
+        // same moment and both waves of a SIMD leave the MFMA pipe idle meanwhile
+        if constexpr (ANR_F32_DMA_SPREAD && cc == 0 && ks > MIDK) {
+          constexpr int eqr = prog_advance<B16, V>(E, Q, mlp_nbuf<B16>() - 1);
+          constexpr int NL = prog_slice_loads<B16, V>(eqr / 1024, eqr % 1024);
+          p.template piece<B16, V, E, Q, ks - MIDK - 1, (NEXT ? NL : ks - MIDK)>();
+        }
+        __builtin_amdgcn_sched_barrier(0);
       });
-      if constexpr (tt % ANR_KSLICE == ANR_KSLICE / 2 - 1) p.template mid<B16, V, E, tt / ANR_KSLICE>();
-      if constexpr (tt % ANR_KSLICE == ANR_KSLICE - 1) p.leave();
+      if constexpr (NC > C) p.template read_w<NCC, NKS, C, NC, NEXT>();  // a wider next entry
+      if constexpr (ks == MIDK) p.template mid<B16, V, E, Q, ANR_F32_DMA_SPREAD != 0>();
+      if constexpr (NEXT) p.leave();
     });
   }
   if constexpr (RELU) {
@@ -1185,6 +1275,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
 
   Pipe p{smem + mlp_ring_off(), mlp_slice_max<B16>(), mlp_nbuf<B16>(), a.wimg, 0, wave, lane, a.pose_woff};
   p.template start<B16, V>();
+  if constexpr (!B16 && ANR_F32_XLAYER) p.template prime_f32<V>();
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int idx = tile * 128 + wave * 16 + pl;
@@ -1296,6 +1387,7 @@ __device__ __forceinline__ void alpha_body(const MlpArgs& a) {
 
   Pipe p{smem + mlp_ring_off(), mlp_slice_max<B16>(), mlp_nbuf<B16>(), a.wimg, 0, wave, lane, a.pose_woff};
   p.template start<B16, V>();
+  if constexpr (!B16 && ANR_F32_XLAYER) p.template prime_f32<V>();
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int idx = tile * 128 + wave * 16 + pl;
