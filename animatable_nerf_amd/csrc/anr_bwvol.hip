@@ -44,19 +44,14 @@ BwvLayout bwv_layout(int nv, int nf, long nvox) {
   const int nprim = std::max(nv, nf);
   L.ncell = (nprim + BWV_CELL - 1) / BWV_CELL;
   const size_t slots = (size_t)L.ncell * BWV_CELL;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.key = take(slots * sizeof(uint64_t));
-  L.perm = take(slots * sizeof(int32_t));
-  L.orig = take(slots * sizeof(int32_t));
-  L.rec = take(slots * sizeof(BwvTri));
-  L.box = take((size_t)L.ncell * sizeof(BwvBox));
-  L.win = take((size_t)nvox * sizeof(int32_t));
-  L.total = o;
+  Carve c;
+  L.key = c.bytes(slots * sizeof(uint64_t));
+  L.perm = c.bytes(slots * sizeof(int32_t));
+  L.orig = c.bytes(slots * sizeof(int32_t));
+  L.rec = c.bytes(slots * sizeof(BwvTri));
+  L.box = c.bytes((size_t)L.ncell * sizeof(BwvBox));
+  L.win = c.bytes((size_t)nvox * sizeof(int32_t));
+  L.total = c.o;
   return L;
 }
 

@@ -42,18 +42,13 @@ EvalLayout eval_layout(int H, int W) {
   L.nb = (int)((hw + EV_PIX - 1) / EV_PIX);
   L.tiles_x = (W + EV_TILE - 1) / EV_TILE;
   L.tiles_y = (H + EV_TILE - 1) / EV_TILE;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.hdr = take(8 * sizeof(int));
-  L.blk = take((size_t)L.nb * sizeof(EvalBlock));
-  L.rowmap = take(hw * sizeof(int));
-  L.sse = take((size_t)2 * EV_SSE_BLOCKS * sizeof(double));
-  L.ssim = take((size_t)3 * L.tiles_x * L.tiles_y * sizeof(double));
-  L.total = o;
+  Carve c;
+  L.hdr = c.bytes(8 * sizeof(int));
+  L.blk = c.bytes((size_t)L.nb * sizeof(EvalBlock));
+  L.rowmap = c.bytes(hw * sizeof(int));
+  L.sse = c.bytes((size_t)2 * EV_SSE_BLOCKS * sizeof(double));
+  L.ssim = c.bytes((size_t)3 * L.tiles_x * L.tiles_y * sizeof(double));
+  L.total = c.o;
   return L;
 }
 

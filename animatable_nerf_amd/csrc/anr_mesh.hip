@@ -142,21 +142,16 @@ AlphaLayout alpha_layout(long n_pts, int chunk_pts, long np) {
   const size_t G = (size_t)((n_pts + 63) / 64), N = G * 64;
   const size_t nch = (G + chunk_pts / 64 - 1) / (chunk_pts / 64);
   AlphaLayout A{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  A.L.counts = take(16);
-  A.L.mask = take(G * 8);
-  A.L.ray_off = take((G + 1) * 4);
-  A.L.block_sum = take(((G + 255) / 256) * 4);
-  A.L.list = take(N * 4);
-  A.L.chunk_min = take(nch * 8);
-  A.L.pbw32 = take((size_t)np * 32 * 4);
-  A.L.fold = take(1280 * 4);
-  A.L.total = o;
+  Carve c;
+  A.L.counts = c.bytes(16);
+  A.L.mask = c.bytes(G * 8);
+  A.L.ray_off = c.bytes((G + 1) * 4);
+  A.L.block_sum = c.bytes(((G + 255) / 256) * 4);
+  A.L.list = c.bytes(N * 4);
+  A.L.chunk_min = c.bytes(nch * 8);
+  A.L.pbw32 = c.bytes((size_t)np * 32 * 4);
+  A.L.fold = c.bytes(1280 * 4);
+  A.L.total = c.o;
   return A;
 }
 
@@ -178,20 +173,15 @@ McLayout mc_layout(int X, int Y, int Z, int pad) {
   const size_t P = (size_t)(X + 2 * pad) * (Y + 2 * pad) * (Z + 2 * pad);
   const size_t nb = (P + 255) / 256;
   McLayout M{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  M.counts = take(16);
-  M.flags = take(P);
-  M.cases = take(P);
-  M.voff = take(P * 4);
-  M.toff = take(P * 4);
-  M.vblock = take(nb * 4);
-  M.tblock = take(nb * 4);
-  M.total = o;
+  Carve c;
+  M.counts = c.bytes(16);
+  M.flags = c.bytes(P);
+  M.cases = c.bytes(P);
+  M.voff = c.bytes(P * 4);
+  M.toff = c.bytes(P * 4);
+  M.vblock = c.bytes(nb * 4);
+  M.tblock = c.bytes(nb * 4);
+  M.total = c.o;
   return M;
 }
 

@@ -67,33 +67,28 @@ struct CcLayout {
 CcLayout cc_layout(long nv, long nt) {
   CcLayout L{};
   const size_t V = (size_t)nv, T = (size_t)nt, S = 3 * T;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.st = take(sizeof(CcState));
-  L.ehead = take((V + 1) * 4);
-  L.vhead = take((V + 1) * 4);
-  L.ecur = take(V * 4);
-  L.vcur = take(V * 4);
-  L.nverts = take(T * 4);
-  L.bad = take(T * 4);
-  L.fkeep = take((T + 1) * 4);
-  L.vkeep = take((V + 1) * 4);
-  L.zero_end = o;
-  L.tri = take(S * 4);
-  L.erec = take(S * 8);
-  L.vrec = take(S * 4);
-  L.parent = take(T * 4);
-  L.root = take(T * 4);
-  L.fbad = take(T);
-  L.bs_e = take((V / 256 + 1) * 4);
-  L.bs_v = take((V / 256 + 1) * 4);
-  L.bs_f = take((T / 256 + 1) * 4);
-  L.bs_k = take((V / 256 + 1) * 4);
-  L.total = o;
+  Carve c;
+  L.st = c.bytes(sizeof(CcState));
+  L.ehead = c.bytes((V + 1) * 4);
+  L.vhead = c.bytes((V + 1) * 4);
+  L.ecur = c.bytes(V * 4);
+  L.vcur = c.bytes(V * 4);
+  L.nverts = c.bytes(T * 4);
+  L.bad = c.bytes(T * 4);
+  L.fkeep = c.bytes((T + 1) * 4);
+  L.vkeep = c.bytes((V + 1) * 4);
+  L.zero_end = c.o;
+  L.tri = c.bytes(S * 4);
+  L.erec = c.bytes(S * 8);
+  L.vrec = c.bytes(S * 4);
+  L.parent = c.bytes(T * 4);
+  L.root = c.bytes(T * 4);
+  L.fbad = c.bytes(T);
+  L.bs_e = c.bytes((V / 256 + 1) * 4);
+  L.bs_v = c.bytes((V / 256 + 1) * 4);
+  L.bs_f = c.bytes((T / 256 + 1) * 4);
+  L.bs_k = c.bytes((V / 256 + 1) * 4);
+  L.total = c.o;
   return L;
 }
 

@@ -71,32 +71,27 @@ MdLayout md_layout(int nf, int npts) {
   L.ncell = (nf + BWV_CELL - 1) / BWV_CELL;
   L.nwaves = md_tiles(nkeys);
   const size_t slots = (size_t)L.ncell * BWV_CELL;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.cum = take((size_t)nf * sizeof(double));
-  L.bsum = take((size_t)md_tiles(nf) * sizeof(double));
-  L.part = take((size_t)md_tiles(nf) * 6 * sizeof(float));
-  L.frame = take(sizeof(MdFrame));
-  L.keyA = take((size_t)nkeys * sizeof(uint64_t));
-  L.keyB = take((size_t)nkeys * sizeof(uint64_t));
-  L.hist = take((size_t)L.nwaves * 256 * sizeof(int32_t));
-  L.hsum = take((size_t)md_tiles((long)L.nwaves * 256) * sizeof(int32_t));
-  L.orig = take(slots * sizeof(int32_t));
-  L.rec = take(slots * sizeof(BwvTri));
-  L.box = take((size_t)L.ncell * sizeof(BwvBox));
-  L.gbox = take((size_t)((L.ncell + MD_GROUP - 1) / MD_GROUP) * sizeof(BwvBox));
-  L.win = take((size_t)npts * sizeof(int32_t));
+  Carve c;
+  L.cum = c.bytes((size_t)nf * sizeof(double));
+  L.bsum = c.bytes((size_t)md_tiles(nf) * sizeof(double));
+  L.part = c.bytes((size_t)md_tiles(nf) * 6 * sizeof(float));
+  L.frame = c.bytes(sizeof(MdFrame));
+  L.keyA = c.bytes((size_t)nkeys * sizeof(uint64_t));
+  L.keyB = c.bytes((size_t)nkeys * sizeof(uint64_t));
+  L.hist = c.bytes((size_t)L.nwaves * 256 * sizeof(int32_t));
+  L.hsum = c.bytes((size_t)md_tiles((long)L.nwaves * 256) * sizeof(int32_t));
+  L.orig = c.bytes(slots * sizeof(int32_t));
+  L.rec = c.bytes(slots * sizeof(BwvTri));
+  L.box = c.bytes((size_t)L.ncell * sizeof(BwvBox));
+  L.gbox = c.bytes((size_t)((L.ncell + MD_GROUP - 1) / MD_GROUP) * sizeof(BwvBox));
+  L.win = c.bytes((size_t)npts * sizeof(int32_t));
   // the composite's own buffers: its samples, their faces, distances and winners
-  L.pts = take((size_t)npts * 3 * sizeof(double));
-  L.sface = take((size_t)npts * sizeof(int32_t));
-  L.dist = take((size_t)npts * sizeof(double));
-  L.kface = take((size_t)npts * sizeof(int32_t));
-  L.status = take(4 * sizeof(int32_t));
-  L.total = o;
+  L.pts = c.bytes((size_t)npts * 3 * sizeof(double));
+  L.sface = c.bytes((size_t)npts * sizeof(int32_t));
+  L.dist = c.bytes((size_t)npts * sizeof(double));
+  L.kface = c.bytes((size_t)npts * sizeof(int32_t));
+  L.status = c.bytes(4 * sizeof(int32_t));
+  L.total = c.o;
   return L;
 }
 

@@ -44,43 +44,38 @@ SLayout slayout(int n_rays, int chunk) {
   SLayout L{};
   const size_t R = (size_t)n_rays, N = R * 64;
   const size_t nch = (R + chunk - 1) / (size_t)std::max(chunk, 1);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.counts = take(16);
-  L.mask = take(R * 8);
-  L.chunk_min = take(nch * 8);
-  L.ray_off = take((R + 1) * 4);
-  L.block_sum = take(((R + 255) / 256) * 4);
-  L.list = take(N * 4);
-  L.knn = take(N * 32);
-  L.tbtab = take(nch * 6 * 4);
-  L.wimg = take(SDF_WN_FLOATS * 4);
-  L.fold = take(768 * 4);
-  L.limg = take(SDF_LIMG_BYTES);
+  Carve c;
+  L.counts = c.bytes(16);
+  L.mask = c.bytes(R * 8);
+  L.chunk_min = c.bytes(nch * 8);
+  L.ray_off = c.bytes((R + 1) * 4);
+  L.block_sum = c.bytes(((R + 255) / 256) * 4);
+  L.list = c.bytes(N * 4);
+  L.knn = c.bytes(N * 32);
+  L.tbtab = c.bytes(nch * 6 * 4);
+  L.wimg = c.bytes(SDF_WN_FLOATS * 4);
+  L.fold = c.bytes(768 * 4);
+  L.limg = c.bytes(SDF_LIMG_BYTES);
   // the fused programs' images: bf16x3 (k_pack_seq) or bf16x6 (k_pack_seq_x6), sized for the larger
-  auto img = [&](int L0, int nl) { return take((size_t)std::max(seq_image_bytes(L0, nl), x6seq_image_bytes(L0, nl))); };
+  auto img = [&](int L0, int nl) { return c.bytes((size_t)std::max(seq_image_bytes(L0, nl), x6seq_image_bytes(L0, nl))); };
   L.rimg = img(ANR_L_RESD0, ANR_RESD_LAYERS);
   L.simg = img(ANR_L_SDF0, ANR_SDF_LAYERS);
   L.gimg = img(ANR_L_SREV0, ANR_SREV_LAYERS);
   L.cimg = img(ANR_L_COL0, ANR_COL_LAYERS);
-  L.resd_rows = take(N * 3 * 4);
-  L.grad_rows = take(N * 3 * 4);
-  L.min_sdf = take(R * 4);
-  L.flags = take(R);
-  L.chunk_cnt = take(nch * 4);
-  L.msk_sdf = take(R * 4);
-  L.msk_label = take(R * 4);
+  L.resd_rows = c.bytes(N * 3 * 4);
+  L.grad_rows = c.bytes(N * 3 * 4);
+  L.min_sdf = c.bytes(R * 4);
+  L.flags = c.bytes(R);
+  L.chunk_cnt = c.bytes(nch * 4);
+  L.msk_sdf = c.bytes(R * 4);
+  L.msk_label = c.bytes(R * 4);
   const long P = (long)std::min<size_t>(N, SDF_BATCH);
   L.P = P;
-  auto f = [&](long w) { return take((size_t)P * w * 4); };
+  auto f = [&](long w) { return c.floats((size_t)P * w); };
   L.ptb = f(8); L.Gr = f(64); L.Ha = f(256); L.Hb = f(256); L.Yr = f(4); L.Xs0 = f(40); L.X4 = f(256);
   L.D = f(8 * 256); L.Y8 = f(264); L.Ga = f(256); L.Gb = f(256); L.Gc = f(256); L.gB = f(40); L.C0 = f(40);
   L.Yc = f(4);
-  L.total = o;
+  L.total = c.o;
   return L;
 }
 

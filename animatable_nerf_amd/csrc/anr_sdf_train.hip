@@ -751,32 +751,26 @@ STLayout stlayout(int R, int chunk) {
   const size_t N = (size_t)R * 64;
   L.N = (long)N;
   const size_t nch = (R + chunk - 1) / (size_t)std::max(chunk, 1);
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  auto f = [&](size_t floats) { return take(floats * 4); };
-  L.counts = take(16); L.mask = take(R * 8); L.chunk_min = take(nch * 8); L.ray_off = take((R + 1) * 4);
-  L.block_sum = take(((N + 255) / 256 + 1) * 4); L.list = take(N * 4); L.knn = take(N * 32); L.tbtab = f(nch * 6);
-  L.wimg = f(SDF_WN_FLOATS); L.fold = f(768); L.inv = take(N * 4);
-  L.ptb = f(N * 8); L.Gr = f(N * 64); L.Hr = f(8 * 2 * N * 256); L.Yr = f(2 * N * 4); L.resd = f(N * 3);
-  L.C0 = f(N * 40); L.Xs0 = f(2 * N * 40); L.Hs = f(8 * 2 * N * 256); L.D = f(8 * N * 256); L.Y8 = f(N * 264);
-  L.Ga = f(N * 256); L.Gb = f(N * 256); L.Gc = f(N * 256); L.gB = f(N * 40); L.grow = f(N * 3);
-  L.Hc = f(4 * N * 256); L.Yc = f(N * 4);
-  L.raw = f(N * 4); L.sdf = f(N); L.draw = f(N * 4); L.drgb = f(R * 3); L.rmin = f(R); L.ramin = take(R * 4);
-  L.rflag = take(R);
-  L.dYc = f(N * 4); L.dHa = f(N * 256); L.dHb = f(N * 256); L.dC0 = f(N * 40); L.dZ8 = f(N * 264); L.ds = f(N);
-  L.dG = f(N * 4); L.rbar = f(N * 4); L.tbar = f(N * 4); L.ttbar = f(N * 4); L.Ab = f(2 * N * 256);
-  L.Zb = f(2 * N * 256); L.AX4 = f(2 * N * 256); L.Ain = f(2 * N * 40); L.dWe = f(SDF_WN_FLOATS); L.bsum = f(4 * 256);
-  L.acc = f(16); L.acc3 = f(4); L.dbeta = f(4); L.zero = take(64);
-  L.oblock = take(((N + 255) / 256 + 1) * 4); L.ptbo = f(N * 8); L.Gro = f(N * 64); L.Grt = f(N * 64);
-  L.ro = f(N * 3); L.og = f(N * 4); L.dog = f(N * 4); L.tdot = f(N * 4); L.Gbar = f(N * 64); L.Yd = f(N * 4);
-  L.gro = f(N * 3);
-  L.wslab = f(wgrad_slab_floats());
-  L.lgimg = take(kLgArena);
-  L.total = o;
+  Carve c;
+  L.counts = c.bytes(16); L.mask = c.bytes(R * 8); L.chunk_min = c.bytes(nch * 8); L.ray_off = c.bytes((R + 1) * 4);
+  L.block_sum = c.bytes(((N + 255) / 256 + 1) * 4); L.list = c.bytes(N * 4); L.knn = c.bytes(N * 32);
+  L.tbtab = c.floats(nch * 6); L.wimg = c.floats(SDF_WN_FLOATS); L.fold = c.floats(768); L.inv = c.bytes(N * 4);
+  L.ptb = c.floats(N * 8); L.Gr = c.floats(N * 64); L.Hr = c.floats(8 * 2 * N * 256); L.Yr = c.floats(2 * N * 4);
+  L.resd = c.floats(N * 3); L.C0 = c.floats(N * 40); L.Xs0 = c.floats(2 * N * 40); L.Hs = c.floats(8 * 2 * N * 256);
+  L.D = c.floats(8 * N * 256); L.Y8 = c.floats(N * 264); L.Ga = c.floats(N * 256); L.Gb = c.floats(N * 256);
+  L.Gc = c.floats(N * 256); L.gB = c.floats(N * 40); L.grow = c.floats(N * 3); L.Hc = c.floats(4 * N * 256);
+  L.Yc = c.floats(N * 4); L.raw = c.floats(N * 4); L.sdf = c.floats(N); L.draw = c.floats(N * 4);
+  L.drgb = c.floats(R * 3); L.rmin = c.floats(R); L.ramin = c.bytes(R * 4); L.rflag = c.bytes(R);
+  L.dYc = c.floats(N * 4); L.dHa = c.floats(N * 256); L.dHb = c.floats(N * 256); L.dC0 = c.floats(N * 40);
+  L.dZ8 = c.floats(N * 264); L.ds = c.floats(N); L.dG = c.floats(N * 4); L.rbar = c.floats(N * 4);
+  L.tbar = c.floats(N * 4); L.ttbar = c.floats(N * 4); L.Ab = c.floats(2 * N * 256); L.Zb = c.floats(2 * N * 256);
+  L.AX4 = c.floats(2 * N * 256); L.Ain = c.floats(2 * N * 40); L.dWe = c.floats(SDF_WN_FLOATS);
+  L.bsum = c.floats(4 * 256); L.acc = c.floats(16); L.acc3 = c.floats(4); L.dbeta = c.floats(4); L.zero = c.bytes(64);
+  L.oblock = c.bytes(((N + 255) / 256 + 1) * 4); L.ptbo = c.floats(N * 8); L.Gro = c.floats(N * 64);
+  L.Grt = c.floats(N * 64); L.ro = c.floats(N * 3); L.og = c.floats(N * 4); L.dog = c.floats(N * 4);
+  L.tdot = c.floats(N * 4); L.Gbar = c.floats(N * 64); L.Yd = c.floats(N * 4); L.gro = c.floats(N * 3);
+  L.wslab = c.floats(wgrad_slab_floats()); L.lgimg = c.bytes(kLgArena);
+  L.total = c.o;
   return L;
 }
 

@@ -64,42 +64,41 @@ struct TLayout {
 // mask DMA reads 4 KiB = 128 rows from the tile's first)
 size_t bits_stride(long N) { return (size_t)((N + 127) / 128 * 128 + 128) * 32; }  // + the last tile's DMA overrun
 
-TLayout tlayout(int n_rays, int chunk, long np, long nt) {
+// f: the frame, for the voxel counts of its pose / T-pose blend-weight volumes
+TLayout tlayout(int n_rays, int chunk, const anr_frame* f) {
   TLayout T{};
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
   T.L = layout(n_rays, chunk, np, nt, true);
-  size_t o = T.L.total;
+  Carve c{T.L.total};
   const size_t N = (size_t)n_rays * 64, R = (size_t)n_rays;
-  auto take = [&](size_t floats) {
-    const size_t at = o;
-    o = align256(o + floats * 4);
-    return at;
-  };
-  T.pt = take(N * 8); T.Gp = take(N * 64); T.Ip = take(N * 32); T.Gv = take(N * 32); T.Lp = take(N * 32);
-  T.lbs = take(N * 16); T.Gt = take(N * 64); T.It = take(N * 32); T.Lt = take(N * 32);
-  T.Hp = take(N * 256 * 8); T.Ht = take(N * 256 * 8); T.Hn = take(N * 256 * 8);
-  T.Feat = take(N * 256); T.Alpha = take(N); T.Lat = take(N * 256); T.View = take(N * 128); T.Rgbl = take(N * 4);
-  T.draw = take(N * 4); T.dRgb = take(N * 4); T.dAlpha = take(N); T.dA16 = take(N * 32); T.dBp = take(N * 24);
-  T.dBt = take(N * 24);
-  T.dLp = take(N * 64); T.dLt = take(N * 64); T.dIt = take(N * 32);  // logit gradients in rows of 64
-  T.dGt = take(N * 64); T.dGt2 = take(N * 64);
+  T.pt = c.floats(N * 8); T.Gp = c.floats(N * 64); T.Ip = c.floats(N * 32); T.Gv = c.floats(N * 32);
+  T.Lp = c.floats(N * 32); T.lbs = c.floats(N * 16); T.Gt = c.floats(N * 64); T.It = c.floats(N * 32);
+  T.Lt = c.floats(N * 32); T.Hp = c.floats(N * 256 * 8); T.Ht = c.floats(N * 256 * 8); T.Hn = c.floats(N * 256 * 8);
+  T.Feat = c.floats(N * 256); T.Alpha = c.floats(N); T.Lat = c.floats(N * 256); T.View = c.floats(N * 128);
+  T.Rgbl = c.floats(N * 4); T.draw = c.floats(N * 4); T.dRgb = c.floats(N * 4); T.dAlpha = c.floats(N);
+  T.dA16 = c.floats(N * 32); T.dBp = c.floats(N * 24); T.dBt = c.floats(N * 24);
+  T.dLp = c.floats(N * 64); T.dLt = c.floats(N * 64); T.dIt = c.floats(N * 32);  // logit gradients in rows of 64
+  T.dGt = c.floats(N * 64); T.dGt2 = c.floats(N * 64);
   // every layer's output gradient has its own slot (the weight-gradient products read them on the
   // side stream while the input-gradient chain moves on)
-  T.dHn = take(N * 256 * 8); T.dHt = take(N * 256 * 8); T.dHp = take(N * 256 * 8);
-  T.dFeat = take(N * 256); T.dLat = take(N * 256); T.dView = take(N * 128);
-  T.ysum = take(8 * 256); T.acc3 = take(4); T.d_rgb = take(R * 3); T.d_pbw = take(N * 24); T.d_tbw = take(N * 24);
-  T.wimg = take((wimg_bytes() + 3) / 4);
-  T.wslab = take(kLaneFloats * kWStreams);
+  T.dHn = c.floats(N * 256 * 8); T.dHt = c.floats(N * 256 * 8); T.dHp = c.floats(N * 256 * 8);
+  T.dFeat = c.floats(N * 256); T.dLat = c.floats(N * 256); T.dView = c.floats(N * 128);
+  T.ysum = c.floats(8 * 256); T.acc3 = c.floats(4); T.d_rgb = c.floats(R * 3); T.d_pbw = c.floats(N * 24);
+  T.d_tbw = c.floats(N * 24);
+  T.wimg = c.floats((wimg_bytes() + 3) / 4);
+  T.wslab = c.floats(kLaneFloats * kWStreams);
   // fused-chain images (anr_tchain.hip): BW / NeRF forward, BW / NeRF input-gradient chains
-  T.tcimg = take((tchain_image_bytes(0) + tchain_image_bytes(1) + tchain_image_bytes(2) + tchain_image_bytes(3) + 3) / 4);
+  T.tcimg = c.floats((tchain_image_bytes(0) + tchain_image_bytes(1) + tchain_image_bytes(2) + tchain_image_bytes(3) + 3) / 4);
   // the forward chains' ReLU mask bits for the input-gradient chains: pose / T-pose BW (8 layers), NeRF
   // (8 layers + view_fc)
-  T.bitsP = take(8 * bits_stride((long)N) / 4); T.bitsT = take(8 * bits_stride((long)N) / 4);
-  T.bitsN = take(9 * bits_stride((long)N) / 4);
+  T.bitsP = c.floats(8 * bits_stride((long)N) / 4); T.bitsT = c.floats(8 * bits_stride((long)N) / 4);
+  T.bitsN = c.floats(9 * bits_stride((long)N) / 4);
   // deterministic mode: per-block loss partials, per-split partials of the generic weight gradients
-  T.lpart = take(loss_part_floats((long)std::max(N, R)));
+  T.lpart = c.floats(loss_part_floats((long)std::max(N, R)));
   T.dscr_floats = det_scratch_floats((long)N);
-  T.dscr = take(T.dscr_floats);
-  T.total = o;
+  T.dscr = c.floats(T.dscr_floats);
+  T.total = c.o;
   return T;
 }
 
@@ -570,19 +569,47 @@ int pack_images(Exec& e, const anr_params* p, char* dst, hipStream_t s, float* w
   return ANR_OK;
 }
 
-TrainBufs bufs(const TLayout& T, char* ws, const anr_frame* f, const float* ray_o, const float* ray_d,
-               const float* near_, const float* far_, int R, const anr_render_opts* o,
-               const anr_samples* x = nullptr) {
+// the executor of one call: precision policy from the options, scratch from the workspace layout T (a
+// TLayout or an ALayout); built in place (Exec holds the queued weight gradients, it is never copied)
+template <class LayoutT>
+void init_exec(Exec& e, const anr_render_opts& o, hipStream_t s, SideStreams* ss, char* ws, const LayoutT& T) {
+  e.s = s;
+  e.bf16 = (o.precision == ANR_BF16 || o.precision == ANR_BF16_ALL) ? 1 : 0;
+  e.pose_fp32 = o.precision == ANR_BF16 ? 1 : 0;
+  e.ss = ss;
+  e.hb = e.bf16;
+  e.dscr = (float*)(ws + T.dscr);
+  e.dscr_floats = T.dscr_floats;
+}
+
+// What one call of a training entry point is about, after its argument checks (train_call below): rays
+// (x NULL) or free samples (x; Network.forward: R groups of 64 samples as one reference chunk, no
+// t_rand, ray pointers NULL), the options in effect, the workspace and its layout.
+struct TrainCall {
+  const anr_params* p;
+  const anr_frame* f;
+  const float *ray_o, *ray_d, *near_, *far_;
+  const anr_samples* x;
+  int R;
+  anr_render_opts o;
+  char* ws;
+  TLayout T;
+};
+
+TrainBufs bufs(const TrainCall& c) {
+  const anr_frame* f = c.f;
+  const TLayout& T = c.T;
+  char* ws = c.ws;
   TrainBufs b{};
-  if (x) {
-    b.wpts = x->wpts; b.vdir = x->viewdir; b.dists = x->dists; b.n_pts = x->n_pts;
+  if (c.x) {
+    b.wpts = c.x->wpts; b.vdir = c.x->viewdir; b.dists = c.x->dists; b.n_pts = c.x->n_pts;
   }
   const Layout& L = T.L;
   b.list = (const int*)(ws + L.list);
   b.n_kept = (const int*)(ws + L.counts);
   b.m_rows = (const int*)(ws + L.counts) + 1;
   b.out_row = (const int*)(ws + L.out_row);
-  b.ray_o = ray_o; b.ray_d = ray_d; b.near_ = near_; b.far_ = far_; b.t_rand = o->t_rand;
+  b.ray_o = c.ray_o; b.ray_d = c.ray_d; b.near_ = c.near_; b.far_ = c.far_; b.t_rand = c.o.t_rand;
   b.R = f->R; b.Th = f->Th; b.A = f->A;
   b.pbw = f->pbw; b.pbounds = f->pbounds; b.tbw = f->tbw; b.tbounds = f->tbounds;
   b.pX = f->pbw_dims[0]; b.pY = f->pbw_dims[1]; b.pZ = f->pbw_dims[2];
@@ -597,7 +624,7 @@ TrainBufs bufs(const TLayout& T, char* ws, const anr_frame* f, const float* ray_
   b.dBp = (float*)(ws + T.dBp); b.dBt = (float*)(ws + T.dBt); b.dLp = (float*)(ws + T.dLp);
   b.dLt = (float*)(ws + T.dLt); b.dIt = (float*)(ws + T.dIt); b.dGt = (float*)(ws + T.dGt);
   b.ldl = 64;
-  b.n_rays = R;
+  b.n_rays = c.R;
   return b;
 }
 
@@ -897,11 +924,63 @@ int chain_bw(const Exec& e, const anr_params* p, const unsigned char* img, const
   return ANR_OK;
 }
 
-// x != NULL: free samples (Network.forward, anr_network_train_fwd): R groups of 64, no compositing
-int train_forward(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
-                  const float* far_, int R, const anr_render_opts* o, const anr_render_out* out, char* ws,
-                  const TLayout& T, hipStream_t s, Exec& e, const anr_samples* x = nullptr,
+// ---- the call context of the entry points -------------------------------------------------------
+// Every entry point: its argument checks, train_call (layout and workspace check: no HIP call so far),
+// then side_streams() / OnMain in the entry point itself (OnMain's destructor joins back into the
+// caller's stream on every return path), init_exec, pack_for.
+// `who`: the public entry point, for the error message
+int train_call(TrainCall& c, const char* who, const anr_params* p, const anr_frame* f, const float* ray_o,
+               const float* ray_d, const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+               void* workspace, size_t ws_bytes) {
+  c = TrainCall{p, f, ray_o, ray_d, near_, far_, nullptr, n_rays, *o, (char*)workspace, tlayout(n_rays, o->chunk, f)};
+  if (ws_bytes < c.T.total) return fail(ANR_E_WORKSPACE, std::string(who) + ": workspace too small");
+  return ANR_OK;
+}
+int train_call(TrainCall& c, const char* who, const anr_params* p, const anr_frame* f, const anr_samples* x,
+               const anr_render_opts* o, void* workspace, size_t ws_bytes) {
+  const int G = (x->n_pts + 63) / 64;
+  anr_render_opts oo = *o;
+  oo.chunk = G;
+  oo.t_rand = nullptr;
+  c = TrainCall{p, f, nullptr, nullptr, nullptr, nullptr, x, G, oo, (char*)workspace, tlayout(G, G, f)};
+  if (ws_bytes < c.T.total) return fail(ANR_E_WORKSPACE, std::string(who) + ": workspace too small");
+  return ANR_OK;
+}
+
+int check_grads(const char* who, float* const* grads, int n = ANR_NUM_TENSORS) {
+  if (!grads) return fail(ANR_E_ARG, std::string(who) + ": NULL grads");
+  for (int i = 0; i < n; ++i)
+    if (!grads[i]) return fail(ANR_E_ARG, std::string(who) + ": NULL grad tensor");
+  return ANR_OK;
+}
+
+// the bf16 images of this call's forward and / or backward; the row-GEMM images only where a product
+// runs outside the chains (a backward alone also needs its forward's mask bits for them)
+int pack_for(const TrainCall& c, Exec& e, hipStream_t s, bool fwd, bool bwd) {
+  const bool covered = chains_cover(e, fwd, bwd) && (fwd || chain_bits_valid(c.ws));
+  return pack_images(e, c.p, c.ws + c.T.wimg, s, (float*)(c.ws + c.T.wslab), kLaneFloats, false, !covered);
+}
+
+// pose-space BW MLP backward (latent row latent_index + 1) from the d logits of k_tr_softmax_bwd_p, then
+// the caller's stream waits for every weight-gradient lane: the end of a backward
+int pose_backward(const TrainCall& c, Exec& e, float* const* grads) {
+  const TLayout& T = c.T;
+  char* ws = c.ws;
+  const long N = (long)c.R * 64;
+  PoseScope ps(e);
+  ANR_TRY(bw_backward(e, c.p->t + 27, grads + 27, (const float*)(ws + T.Gp), (const float*)(ws + T.Hp),
+                      (const float*)(ws + T.dLp), (float*)(ws + T.dHp), nullptr, N * 256, nullptr, false, N,
+                      (float*)(ws + T.ysum) + 1024, c.f->latent_index, 1, 64, pose_bchain(e, ws, T), pose_bits(ws, T)));
+  return e.join_w();
+}
+
+// c.x != NULL: free samples (Network.forward, anr_network_train_fwd): R groups of 64, no compositing
+int train_forward(const TrainCall& c, const anr_render_out* out, hipStream_t s, Exec& e,
                   const RaySplit* split = nullptr) {
+  const anr_params* p = c.p;
+  const TLayout& T = c.T;
+  char* ws = c.ws;
+  const int R = c.R;
   float4* raw = (float4*)(ws + T.L.raw);
   const bool fchain = e.hb && fchain_on() && R > 0;
   note_chain_bits(ws, fchain);
@@ -920,12 +999,12 @@ int train_forward(const anr_params* p, const anr_frame* f, const float* ray_o, c
       e.bimg = true;
     }
   }
-  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, R, o, ws, T.L, raw, s, x, split));
+  ANR_TRY(stage_frontend(p, c.f, c.ray_o, c.ray_d, c.near_, c.far_, R, &c.o, ws, T.L, raw, s, c.x, split));
   const long N = (long)R * 64;
   e.n_dev = (const int*)(ws + T.L.counts);
   e.cap = (int)N;
   const int n = e.grid_n();
-  TrainBufs b = bufs(T, ws, f, ray_o, ray_d, near_, far_, R, o, x);
+  TrainBufs b = bufs(c);
   b.hb = e.hb;
   b.hbp = e.hb && !e.pose_fp32;
   const int g1 = (n + 255) / 256;
@@ -1011,23 +1090,26 @@ int train_forward(const anr_params* p, const anr_frame* f, const float* ray_o, c
     hipLaunchKernelGGL(k_tr_raw, dim3(g1), dim3(256), 0, s, b);
     ANR_TRY(check_launch("k_tr_raw"));
   }
-  ANR_TRY(stage_alpha_ind(R, o, ws, T.L, s, split));
+  ANR_TRY(stage_alpha_ind(R, &c.o, ws, T.L, s, split));
   ANR_TRY(order(e.ss, s, s2));  // join: the tbw rows
-  if (x) return ANR_OK;
-  return stage_composite(near_, far_, R, o, raw, out, nullptr, s);
+  if (c.x) return ANR_OK;
+  return stage_composite(c.near_, c.far_, R, &c.o, raw, out, nullptr, s);
 }
 
-// x != NULL: free samples; the upstream gradient is d raw (x->n_pts, 4) (NULL: zero) instead of d rgb_map
-int train_backward(const anr_params* p, float* const* g, const anr_frame* f, const float* ray_o, const float* ray_d,
-                   const float* near_, const float* far_, int R, const anr_render_opts* o, const float* d_rgb,
-                   const float* d_pbw, const float* d_tbw, char* ws, const TLayout& T, hipStream_t s, Exec& e,
-                   const anr_samples* x = nullptr, const float* d_raw = nullptr, hipEvent_t nerf_done = nullptr) {
+// c.x != NULL: free samples; the upstream gradient is d raw (x->n_pts, 4) (NULL: zero) instead of d rgb_map
+int train_backward(const TrainCall& c, float* const* g, const float* d_rgb, const float* d_pbw, const float* d_tbw,
+                   hipStream_t s, Exec& e, const float* d_raw = nullptr, hipEvent_t nerf_done = nullptr) {
+  const anr_params* p = c.p;
+  const anr_samples* x = c.x;
+  const TLayout& T = c.T;
+  char* ws = c.ws;
+  const int R = c.R;
   const long N = (long)R * 64;
   e.n_dev = (const int*)(ws + T.L.counts);
   e.cap = (int)N;
   const int n = e.grid_n();
   const long S = N * 256;
-  TrainBufs b = bufs(T, ws, f, ray_o, ray_d, near_, far_, R, o, x);
+  TrainBufs b = bufs(c);
   b.hb = e.hb;
   b.d_rgb_map = d_rgb; b.d_pbw = d_pbw; b.d_tbw = d_tbw;
   const int g1 = (n + 255) / 256;
@@ -1129,7 +1211,7 @@ int train_backward(const anr_params* p, float* const* g, const anr_frame* f, con
   {
     float* ys = ysum + 512;
     ANR_TRY(e.latent_rows(ys, g[21], 384, 0, 256, dLat, 256, Feat, 256, 256, g[22], hb & (BF_A | BF_X),
-                          Exec::LatentPost{ys, PT(21), 384, 256, 256, PT(0), f->latent_index, 0, g[21], g[0]}));
+                          Exec::LatentPost{ys, PT(21), 384, 256, 256, PT(0), c.f->latent_index, 0, g[21], g[0]}));
   }
   if (!bchain)
     ANR_TRY(e.xgrad(dFeat, 256, 256, dLat, 256, 256, PT(21), 384, 0, nullptr, 0, false, nullptr, 0, 0, nullptr, 0,
@@ -1195,27 +1277,20 @@ struct ALayout {
 
 ALayout alayout(long N) {
   ALayout T{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
+  Carve c;
   const size_t n = (size_t)N;
-  T.counts = take(16); T.amax = take(8); T.acc = take(16);
-  T.pt = take(n * 32); T.Gp = take(n * 256); T.Ip = take(n * 128); T.Lp = take(n * 128); T.Bp = take(n * 96);
-  T.lbs = take(n * 64); T.Gt = take(n * 256); T.It = take(n * 128); T.Lt = take(n * 128); T.Bt = take(n * 96);
-  T.Hp = take(n * 256 * 8 * 4); T.Ht = take(n * 256 * 8 * 4); T.Hn = take(n * 256 * 2 * 4);
-  T.Alpha = take(n * 4); T.sel = take(n * 4);
-  T.dBp = take(n * 96); T.dBt = take(n * 96); T.dLp = take(n * 128); T.dLt = take(n * 128); T.dIt = take(n * 128);
-  T.dGt = take(n * 256); T.dA = take(n * 1024); T.dB = take(n * 1024); T.ysum = take(8 * 256 * 4);
-  T.fold = take(1280 * 4);
-  T.wimg = take(wimg_bytes());
-  T.wslab = take(wgrad_slab_floats() * 4);
-  T.lpart = take(loss_part_floats(N) * 4);
+  T.counts = c.bytes(16); T.amax = c.bytes(8); T.acc = c.bytes(16); T.pt = c.bytes(n * 32); T.Gp = c.bytes(n * 256);
+  T.Ip = c.bytes(n * 128); T.Lp = c.bytes(n * 128); T.Bp = c.bytes(n * 96); T.lbs = c.bytes(n * 64);
+  T.Gt = c.bytes(n * 256); T.It = c.bytes(n * 128); T.Lt = c.bytes(n * 128); T.Bt = c.bytes(n * 96);
+  T.Hp = c.bytes(n * 256 * 8 * 4); T.Ht = c.bytes(n * 256 * 8 * 4); T.Hn = c.bytes(n * 256 * 2 * 4);
+  T.Alpha = c.bytes(n * 4); T.sel = c.bytes(n * 4); T.dBp = c.bytes(n * 96); T.dBt = c.bytes(n * 96);
+  T.dLp = c.bytes(n * 128); T.dLt = c.bytes(n * 128); T.dIt = c.bytes(n * 128); T.dGt = c.bytes(n * 256);
+  T.dA = c.bytes(n * 1024); T.dB = c.bytes(n * 1024); T.ysum = c.bytes(8 * 256 * 4); T.fold = c.bytes(1280 * 4);
+  T.wimg = c.bytes(wimg_bytes()); T.wslab = c.bytes(wgrad_slab_floats() * 4);
+  T.lpart = c.bytes(loss_part_floats(N) * 4);
   T.dscr_floats = det_scratch_floats(N);
-  T.dscr = take(T.dscr_floats * 4);
-  T.total = o;
+  T.dscr = c.bytes(T.dscr_floats * 4);
+  T.total = c.o;
   return T;
 }
 
@@ -1332,9 +1407,7 @@ int anr_train_deterministic(int on) {
 
 size_t anr_train_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f) {
   if (!o || !f || n_rays <= 0) return 0;
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  return tlayout(n_rays, o->chunk, np, nt).total;
+  return tlayout(n_rays, o->chunk, f).total;
 }
 
 int anr_train_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
@@ -1342,24 +1415,16 @@ int anr_train_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, c
                   size_t ws_bytes, void* stream) {
   ANR_TRY(check_args(p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace));
   if (!out || !out->rgb_map || !out->acc_map || !out->depth_map) return fail(ANR_E_ARG, "anr_train_fwd: NULL output");
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const TLayout T = tlayout(n_rays, o->chunk, np, nt);
-  if (ws_bytes < T.total) return fail(ANR_E_WORKSPACE, "anr_train_fwd: workspace too small");
+  TrainCall c;
+  ANR_TRY(train_call(c, "anr_train_fwd", p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace, ws_bytes));
   OnMain om(side_streams(), (hipStream_t)stream);
   ANR_TRY(om.rc);
-  hipStream_t s = om.s;
-  char* ws = (char*)workspace;
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.ss = om.ss;
-  e.hb = e.bf16;
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
-  ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
-                      !chains_cover(e, true, false)));
-  ANR_TRY(train_forward(p, f, ray_o, ray_d, near_, far_, n_rays, o, out, ws, T, s, e));
-  if (out->raw &&
-      hipMemcpyAsync(out->raw, ws + T.L.raw, (size_t)n_rays * 64 * 16, hipMemcpyDeviceToDevice, s) != hipSuccess)
+  Exec e{};
+  init_exec(e, c.o, om.s, om.ss, c.ws, c.T);
+  ANR_TRY(pack_for(c, e, om.s, true, false));
+  ANR_TRY(train_forward(c, out, om.s, e));
+  if (out->raw && hipMemcpyAsync(out->raw, c.ws + c.T.L.raw, (size_t)n_rays * 64 * 16, hipMemcpyDeviceToDevice,
+                                 om.s) != hipSuccess)
     return fail(ANR_E_HIP, "raw copy failed");
   return ANR_OK;
 }
@@ -1368,33 +1433,16 @@ int anr_train_bwd(const anr_params* p, float* const* grads, const anr_frame* f, 
                   const float* near_, const float* far_, int n_rays, const anr_render_opts* o, const float* d_rgb_map,
                   const float* d_pbw, const float* d_tbw, void* workspace, size_t ws_bytes, void* stream) {
   ANR_TRY(check_args(p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace));
-  if (!grads) return fail(ANR_E_ARG, "anr_train_bwd: NULL grads");
-  for (int i = 0; i < ANR_NUM_TENSORS; ++i)
-    if (!grads[i]) return fail(ANR_E_ARG, "anr_train_bwd: NULL grad tensor");
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const TLayout T = tlayout(n_rays, o->chunk, np, nt);
-  if (ws_bytes < T.total) return fail(ANR_E_WORKSPACE, "anr_train_bwd: workspace too small");
+  ANR_TRY(check_grads("anr_train_bwd", grads));
+  TrainCall c;
+  ANR_TRY(train_call(c, "anr_train_bwd", p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace, ws_bytes));
   OnMain om(side_streams(), (hipStream_t)stream);
   ANR_TRY(om.rc);
-  hipStream_t s = om.s;
-  char* ws = (char*)workspace;
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.ss = om.ss;
-  e.hb = e.bf16;
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
-  ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
-                      !(chains_cover(e, false, true) && chain_bits_valid(ws))));
-  ANR_TRY(train_backward(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, d_rgb_map, d_pbw, d_tbw, ws, T, s, e));
-  // pose BW MLP backward: d logits were produced by k_tr_softmax_bwd_p
-  const long N = (long)n_rays * 64;
-  float* ysum = (float*)(ws + T.ysum);
-  PoseScope ps(e);
-  ANR_TRY(bw_backward(e, p->t + 27, grads + 27, (const float*)(ws + T.Gp), (const float*)(ws + T.Hp), (const float*)(ws + T.dLp),
-                      (float*)(ws + T.dHp), nullptr, N * 256, nullptr, false, N, ysum + 1024, f->latent_index, 1, 64,
-                      pose_bchain(e, ws, T), pose_bits(ws, T)));
-  return e.join_w();
+  Exec e{};
+  init_exec(e, c.o, om.s, om.ss, c.ws, c.T);
+  ANR_TRY(pack_for(c, e, om.s, false, true));
+  ANR_TRY(train_backward(c, grads, d_rgb_map, d_pbw, d_tbw, om.s, e));
+  return pose_backward(c, e, grads);
 }
 
 int anr_train_step(const anr_params* p, float* const* grads, const anr_frame* f, const float* ray_o,
@@ -1410,24 +1458,21 @@ int anr_train_step(const anr_params* p, float* const* grads, const anr_frame* f,
 namespace {
 
 // one training step, issued to s (eagerly, or into a graph capture whose origin is s)
-int train_step_body(const anr_params* p, float* const* grads, const anr_frame* f, const float* ray_o,
-                    const float* ray_d, const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
-                    const float* rgb_gt, const uint8_t* mask_at_box, const anr_render_out* out, float* loss3,
-                    hipEvent_t nerf_done, char* ws, const TLayout& T, hipStream_t s, SideStreams* ss,
+int train_step_body(const TrainCall& c, float* const* grads, const float* rgb_gt, const uint8_t* mask_at_box,
+                    const anr_render_out* out, float* loss3, hipEvent_t nerf_done, hipStream_t s, SideStreams* ss,
                     const RaySplit* split = nullptr) {
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.ss = ss;
-  e.hb = e.bf16;
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
-  ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
-                      !chains_cover(e, true, true)));
+  const TLayout& T = c.T;
+  char* ws = c.ws;
+  const int n_rays = c.R;
+  Exec e{};
+  init_exec(e, c.o, s, ss, ws, T);
+  ANR_TRY(pack_for(c, e, s, true, true));
   float* acc3 = (float*)(ws + T.acc3);
   e.pz4 = acc3;
   e.pz2048 = (float*)(ws + T.ysum);
-  ANR_TRY(train_forward(p, f, ray_o, ray_d, near_, far_, n_rays, o, out, ws, T, s, e, nullptr, split));
+  ANR_TRY(train_forward(c, out, s, e, split));
   // fused losses (tpose_trainer.py:50-63) and their upstream gradients
-  TrainBufs b = bufs(T, ws, f, ray_o, ray_d, near_, far_, n_rays, o);
+  TrainBufs b = bufs(c);
   b.rgb_map = out->rgb_map;
   if (!e.prezeroed && hipMemsetAsync(acc3, 0, 16, s) != hipSuccess) return fail(ANR_E_HIP, "memset");
   const long N = (long)n_rays * 64;
@@ -1455,14 +1500,8 @@ int train_step_body(const anr_params* p, float* const* grads, const anr_frame* f
   hipLaunchKernelGGL(k_tr_loss_grads, dim3(gx, 2), dim3(256), 0, s, b, rgb_gt, mask_at_box, (const float*)acc3, d_rgb,
                      d_pbw, d_tbw);
   ANR_TRY(check_launch("k_tr_loss_grads"));
-  ANR_TRY(train_backward(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, d_rgb, d_pbw, d_tbw, ws, T, s, e, nullptr,
-                         nullptr, nerf_done));
-  float* ysum = (float*)(ws + T.ysum);
-  PoseScope ps(e);
-  ANR_TRY(bw_backward(e, p->t + 27, grads + 27, (const float*)(ws + T.Gp), (const float*)(ws + T.Hp), (const float*)(ws + T.dLp),
-                      (float*)(ws + T.dHp), nullptr, N * 256, nullptr, false, N, ysum + 1024, f->latent_index, 1, 64,
-                      pose_bchain(e, ws, T), pose_bits(ws, T)));
-  return e.join_w();
+  ANR_TRY(train_backward(c, grads, d_rgb, d_pbw, d_tbw, s, e, nullptr, nerf_done));
+  return pose_backward(c, e, grads);
 }
 
 // ---- step graphs ----------------------------------------------------------------------------------
@@ -1506,14 +1545,10 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
   ANR_TRY(check_args(p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace));
   if (!grads || !rgb_gt || !loss3 || !out || !out->rgb_map || !out->acc_map || !out->depth_map)
     return fail(ANR_E_ARG, "anr_train_step: NULL argument");
-  for (int i = 0; i < ANR_NUM_TENSORS; ++i)
-    if (!grads[i]) return fail(ANR_E_ARG, "anr_train_step: NULL grad tensor");
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const TLayout T = tlayout(n_rays, o->chunk, np, nt);
-  if (ws_bytes < T.total) return fail(ANR_E_WORKSPACE, "anr_train_step: workspace too small");
+  ANR_TRY(check_grads("anr_train_step", grads));
+  TrainCall c;
+  ANR_TRY(train_call(c, "anr_train_step", p, f, ray_o, ray_d, near_, far_, n_rays, o, workspace, ws_bytes));
   hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
   SideStreams* ss = side_streams();
   if (hooks && hooks->struct_size != sizeof(anr_train_hooks))
     return fail(ANR_E_ARG, "anr_train_step_hooked: hooks->struct_size != sizeof(anr_train_hooks) (header version mismatch)");
@@ -1535,8 +1570,7 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
     // (a ray split's reduce hook is handed the main stream and issues its collectives there)
     OnMain om(ss, s);
     ANR_TRY(om.rc);
-    return train_step_body(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, rgb_gt, mask_at_box, out, loss3,
-                           nerf_done, ws, T, om.s, ss, splitting ? &split : nullptr);
+    return train_step_body(c, grads, rgb_gt, mask_at_box, out, loss3, nerf_done, om.s, ss, splitting ? &split : nullptr);
   }
   std::string key;
   int dev = 0;
@@ -1566,8 +1600,7 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
     if (G.seen.size() > 64) G.seen.erase(G.seen.begin());
     OnMain om(ss, s);
     ANR_TRY(om.rc);
-    return train_step_body(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, rgb_gt, mask_at_box, out, loss3,
-                           nullptr, ws, T, om.s, ss);
+    return train_step_body(c, grads, rgb_gt, mask_at_box, out, loss3, nullptr, om.s, ss);
   }
   G.seen.erase(seen);
   // second sighting: capture, instantiate, launch
@@ -1575,8 +1608,7 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
     return fail(ANR_E_HIP, "anr_train_step: capture stream");
   if (hipStreamBeginCapture(ss->cap, hipStreamCaptureModeRelaxed) != hipSuccess)
     return fail(ANR_E_HIP, "anr_train_step: hipStreamBeginCapture failed");
-  const int rc = train_step_body(p, grads, f, ray_o, ray_d, near_, far_, n_rays, o, rgb_gt, mask_at_box, out, loss3,
-                                 nullptr, ws, T, ss->cap, ss);
+  const int rc = train_step_body(c, grads, rgb_gt, mask_at_box, out, loss3, nullptr, ss->cap, ss);
   hipGraph_t graph = nullptr;
   const hipError_t ec = hipStreamEndCapture(ss->cap, &graph);
   if (rc != ANR_OK) {
@@ -1610,7 +1642,8 @@ int anr_anim_step(const anr_params* p, float* const* grads, const anr_frame* f, 
   for (int i = 0; i < ANR_NUM_TENSORS; ++i)
     if (!p->t[i]) return fail(ANR_E_ARG, "anr_anim_step: NULL parameter tensor");
   for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-    if (!p->novel[i] || !grads[i]) return fail(ANR_E_ARG, "anr_anim_step: the novel_pose_bw tensors and their grads are required");
+    if (!p->novel[i]) return fail(ANR_E_ARG, "anr_anim_step: the novel_pose_bw tensors are required");
+  ANR_TRY(check_grads("anr_anim_step", grads, ANR_NUM_NOVEL_TENSORS));
   if (!f->A || !f->R || !f->Th || !f->pbw || !f->tbw || !f->pbounds || !f->tbounds || !f->bw_latent_index)
     return fail(ANR_E_ARG, "anr_anim_step: NULL frame tensor");
   for (int i = 0; i < 3; ++i)
@@ -1637,9 +1670,9 @@ int anr_anim_step(const anr_params* p, float* const* grads, const anr_frame* f, 
   pa.bw_latent_index = f->bw_latent_index;
   hipLaunchKernelGGL(k_prep, dim3(prep_blocks(0, 0)), dim3(256), 0, s, pa);
   ANR_TRY(check_launch("k_prep(anim)"));
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
+  Exec e{};
+  init_exec(e, *o, s, nullptr, ws, T);  // one stream, one weight-gradient lane
+  e.hb = 0;                             // fp32 rows under every policy
   ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), wgrad_slab_floats(), true));
   ANR_TRY(anim_path(p, grads, f, wpts, n_obs, true, o, ws, T, s, e));
   ANR_TRY(anim_path(p, grads, f, tpts, n_can, false, o, ws, T, s, e));
@@ -1662,36 +1695,22 @@ static int check_network_train(const anr_params* p, const anr_frame* f, const an
 size_t anr_network_train_workspace_bytes(int n_pts, const anr_render_opts* o, const anr_frame* f) {
   if (!o || !f || n_pts <= 0) return 0;
   const int G = (n_pts + 63) / 64;
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  return tlayout(G, G, np, nt).total;
+  return tlayout(G, G, f).total;
 }
 
 int anr_network_train_fwd(const anr_params* p, const anr_frame* f, const anr_samples* x, const anr_render_opts* o,
                           float* raw, void* workspace, size_t ws_bytes, void* stream) {
   ANR_TRY(check_network_train(p, f, x, o, workspace));
   if (!raw) return fail(ANR_E_ARG, "anr_network_train_fwd: NULL raw");
-  const int G = (x->n_pts + 63) / 64;
-  anr_render_opts oo = *o;
-  oo.chunk = G;
-  oo.t_rand = nullptr;
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const TLayout T = tlayout(G, G, np, nt);
-  if (ws_bytes < T.total) return fail(ANR_E_WORKSPACE, "anr_network_train_fwd: workspace too small");
+  TrainCall c;
+  ANR_TRY(train_call(c, "anr_network_train_fwd", p, f, x, o, workspace, ws_bytes));
   OnMain om(side_streams(), (hipStream_t)stream);
   ANR_TRY(om.rc);
-  hipStream_t s = om.s;
-  char* ws = (char*)workspace;
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.ss = om.ss;
-  e.hb = e.bf16;
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
-  ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
-                      !chains_cover(e, true, false)));
-  ANR_TRY(train_forward(p, f, nullptr, nullptr, nullptr, nullptr, G, &oo, nullptr, ws, T, s, e, x));
-  if (hipMemcpyAsync(raw, ws + T.L.raw, (size_t)x->n_pts * 16, hipMemcpyDeviceToDevice, s) != hipSuccess)
+  Exec e{};
+  init_exec(e, c.o, om.s, om.ss, c.ws, c.T);
+  ANR_TRY(pack_for(c, e, om.s, true, false));
+  ANR_TRY(train_forward(c, nullptr, om.s, e));
+  if (hipMemcpyAsync(raw, c.ws + c.T.L.raw, (size_t)x->n_pts * 16, hipMemcpyDeviceToDevice, om.s) != hipSuccess)
     return fail(ANR_E_HIP, "anr_network_train_fwd: raw copy failed");
   return ANR_OK;
 }
@@ -1700,54 +1719,34 @@ int anr_network_train_bwd(const anr_params* p, float* const* grads, const anr_fr
                           const anr_render_opts* o, const float* d_raw, const float* d_pbw, const float* d_tbw,
                           void* workspace, size_t ws_bytes, void* stream) {
   ANR_TRY(check_network_train(p, f, x, o, workspace));
-  if (!grads) return fail(ANR_E_ARG, "anr_network_train_bwd: NULL grads");
-  for (int i = 0; i < ANR_NUM_TENSORS; ++i)
-    if (!grads[i]) return fail(ANR_E_ARG, "anr_network_train_bwd: NULL grad tensor");
-  const int G = (x->n_pts + 63) / 64;
-  anr_render_opts oo = *o;
-  oo.chunk = G;
-  oo.t_rand = nullptr;
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const TLayout T = tlayout(G, G, np, nt);
-  if (ws_bytes < T.total) return fail(ANR_E_WORKSPACE, "anr_network_train_bwd: workspace too small");
+  ANR_TRY(check_grads("anr_network_train_bwd", grads));
+  TrainCall c;
+  ANR_TRY(train_call(c, "anr_network_train_bwd", p, f, x, o, workspace, ws_bytes));
   OnMain om(side_streams(), (hipStream_t)stream);
   ANR_TRY(om.rc);
-  hipStream_t s = om.s;
-  char* ws = (char*)workspace;
-  Exec e{s, 0, (o->precision == ANR_BF16 || o->precision == ANR_BF16_ALL) ? 1 : 0, o->precision == ANR_BF16 ? 1 : 0};
-  e.ss = om.ss;
-  e.hb = e.bf16;
-  e.dscr = (float*)(ws + T.dscr);
-  e.dscr_floats = T.dscr_floats;
-  ANR_TRY(pack_images(e, p, ws + T.wimg, s, (float*)(ws + T.wslab), kLaneFloats, false,
-                      !(chains_cover(e, false, true) && chain_bits_valid(ws))));
-  ANR_TRY(train_backward(p, grads, f, nullptr, nullptr, nullptr, nullptr, G, &oo, nullptr, d_pbw, d_tbw, ws, T, s, e, x,
-                         d_raw));
-  const long N = (long)G * 64;
-  float* ysum = (float*)(ws + T.ysum);
-  PoseScope ps(e);
-  ANR_TRY(bw_backward(e, p->t + 27, grads + 27, (const float*)(ws + T.Gp), (const float*)(ws + T.Hp),
-                      (const float*)(ws + T.dLp), (float*)(ws + T.dHp), nullptr, N * 256, nullptr, false, N, ysum + 1024,
-                      f->latent_index, 1, 64, pose_bchain(e, ws, T), pose_bits(ws, T)));
-  return e.join_w();
+  Exec e{};
+  init_exec(e, c.o, om.s, om.ss, c.ws, c.T);
+  ANR_TRY(pack_for(c, e, om.s, false, true));
+  ANR_TRY(train_backward(c, grads, nullptr, d_pbw, d_tbw, om.s, e, d_raw));
+  return pose_backward(c, e, grads);
 }
 
 // ---- free-point helpers: calculate_neural_blend_weights / novel_pose_bw, TPoseHuman.calculate_alpha --
-static size_t points_take(size_t& o, size_t floats) {
-  const size_t at = o;
-  o = align256(o + floats * 4);
-  return at;
+// gamma rows G, initial SMPL-weight rows I, logits Lg, the hidden rows H of one MLP, the two folded biases
+struct PLayout {
+  size_t G, I, Lg, H, fold, total;
+};
+static PLayout playout(int n) {
+  const size_t N = (size_t)n;
+  Carve c;
+  PLayout P{};
+  P.G = c.floats(N * 64); P.I = c.floats(N * 32); P.Lg = c.floats(N * 32); P.H = c.floats(N * 256 * 8);
+  P.fold = c.floats(512);
+  P.total = c.o;
+  return P;
 }
 
-size_t anr_points_workspace_bytes(int n) {
-  if (n <= 0) return 0;
-  size_t o = 0;
-  const size_t N = (size_t)n;
-  points_take(o, N * 64); points_take(o, N * 32); points_take(o, N * 32); points_take(o, N * 256 * 8);
-  points_take(o, 512);
-  return o;
-}
+size_t anr_points_workspace_bytes(int n) { return n <= 0 ? 0 : playout(n).total; }
 
 int anr_blend_weights(const anr_params* p, int field, const float* pts, const float* smpl_bw, int n,
                       const int64_t* latent_row, int row_add, float* bw, void* workspace, size_t ws_bytes, void* stream) {
@@ -1756,15 +1755,11 @@ int anr_blend_weights(const anr_params* p, int field, const float* pts, const fl
   const float* const* W = field ? p->novel : p->t + 27;
   for (int i = 0; i < 19; ++i)
     if (!W[i]) return fail(ANR_E_ARG, "anr_blend_weights: NULL blend-weight field tensor");
-  if (ws_bytes < anr_points_workspace_bytes(n)) return fail(ANR_E_WORKSPACE, "anr_blend_weights: workspace too small");
+  const PLayout P = playout(n);
+  if (ws_bytes < P.total) return fail(ANR_E_WORKSPACE, "anr_blend_weights: workspace too small");
   char* ws = (char*)workspace;
-  size_t o = 0;
-  const size_t N = (size_t)n;
-  float* G = (float*)(ws + points_take(o, N * 64));
-  float* I = (float*)(ws + points_take(o, N * 32));
-  float* Lg = (float*)(ws + points_take(o, N * 32));
-  float* H = (float*)(ws + points_take(o, N * 256 * 8));
-  float* fold = (float*)(ws + points_take(o, 512));
+  float *G = (float*)(ws + P.G), *I = (float*)(ws + P.I), *Lg = (float*)(ws + P.Lg), *H = (float*)(ws + P.H);
+  float* fold = (float*)(ws + P.fold);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_pt_prep, dim3((n + 3) / 4), dim3(256), 0, s, pts, smpl_bw, n, G, I);
   FoldArgs fa{W[1], W[2], W[11], W[12], W[0], latent_row, row_add, fold};
@@ -1781,14 +1776,10 @@ int anr_canonical_alpha(const anr_params* p, const float* pts, int n, float* alp
   if (!p || !pts || !alpha || !workspace || n <= 0) return fail(ANR_E_ARG, "anr_canonical_alpha: bad arguments");
   for (int i = 1; i <= 18; ++i)
     if (!p->t[i]) return fail(ANR_E_ARG, "anr_canonical_alpha: NULL parameter tensor");
-  if (ws_bytes < anr_points_workspace_bytes(n)) return fail(ANR_E_WORKSPACE, "anr_canonical_alpha: workspace too small");
+  const PLayout P = playout(n);
+  if (ws_bytes < P.total) return fail(ANR_E_WORKSPACE, "anr_canonical_alpha: workspace too small");
   char* ws = (char*)workspace;
-  size_t o = 0;
-  const size_t N = (size_t)n;
-  float* G = (float*)(ws + points_take(o, N * 64));
-  points_take(o, N * 32);
-  points_take(o, N * 32);
-  float* H = (float*)(ws + points_take(o, N * 256 * 8));
+  float *G = (float*)(ws + P.G), *H = (float*)(ws + P.H);
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(k_pt_prep, dim3((n + 3) / 4), dim3(256), 0, s, pts, (const float*)nullptr, n, G, (float*)nullptr);
   ANR_TRY(check_launch("k_pt_prep"));

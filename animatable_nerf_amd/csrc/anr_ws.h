@@ -12,6 +12,18 @@ namespace anr {
 
 inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Carves a workspace into 256-B aligned regions, in call order: each call returns the offset of its
+// region; `o` is then the total so far. A layout that continues another's starts at that one's total.
+struct Carve {
+  size_t o = 0;
+  size_t bytes(size_t n) {
+    const size_t at = o;
+    o = align256(o + n);
+    return at;
+  }
+  size_t floats(size_t n) { return bytes(n * 4); }
+};
+
 // Workspace layout. Fields up to `tbw_rows` depend only on n_rays (anr_render_counts/bw_rows).
 struct Layout {
   size_t counts, mask, ray_off, block_sum, list, sigma, flags, block_sum2, out_row, pbw_rows, tbw_rows;
@@ -21,32 +33,27 @@ struct Layout {
 inline Layout layout(int n_rays, int chunk, long np, long nt, bool need_raw) {
   Layout L{};
   const size_t R = (size_t)n_rays, N = R * 64;
-  size_t o = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = o;
-    o = align256(o + bytes);
-    return at;
-  };
-  L.counts = take(16);
-  L.mask = take(R * 8);
-  L.ray_off = take((R + 1) * 4);
-  L.block_sum = take(((R + 255) / 256) * 4);
-  L.list = take(N * 4);
-  L.sigma = take(N * 4);
-  L.flags = take(N);
-  L.block_sum2 = take(((N + 1023) / 1024) * 4);
-  L.out_row = take(N * 4);
-  L.pbw_rows = take(N * 24 * 4);
-  L.tbw_rows = take(N * 24 * 4);
+  Carve c;
+  L.counts = c.bytes(16);
+  L.mask = c.bytes(R * 8);
+  L.ray_off = c.bytes((R + 1) * 4);
+  L.block_sum = c.bytes(((R + 255) / 256) * 4);
+  L.list = c.bytes(N * 4);
+  L.sigma = c.bytes(N * 4);
+  L.flags = c.bytes(N);
+  L.block_sum2 = c.bytes(((N + 1023) / 1024) * 4);
+  L.out_row = c.bytes(N * 4);
+  L.pbw_rows = c.bytes(N * 24 * 4);
+  L.tbw_rows = c.bytes(N * 24 * 4);
   const size_t nch = (R + chunk - 1) / (chunk > 0 ? chunk : 1);
-  L.chunk_min = take(nch * 8);
-  L.chunk_max = take(nch * 8);
-  L.raw = need_raw ? take(N * 16) : 0;
-  L.pbw32 = take((size_t)np * 32 * 4);
-  L.tbw32 = take((size_t)nt * 32 * 4);
-  L.pn24 = take((size_t)np * 4);
-  L.fold = take(ANR_FOLD_FLOATS * 4);
-  L.total = o;
+  L.chunk_min = c.bytes(nch * 8);
+  L.chunk_max = c.bytes(nch * 8);
+  L.raw = need_raw ? c.bytes(N * 16) : 0;
+  L.pbw32 = c.bytes((size_t)np * 32 * 4);
+  L.tbw32 = c.bytes((size_t)nt * 32 * 4);
+  L.pn24 = c.bytes((size_t)np * 4);
+  L.fold = c.bytes(ANR_FOLD_FLOATS * 4);
+  L.total = c.o;
   return L;
 }
 
