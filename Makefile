@@ -14,10 +14,10 @@ DEPS := $(OBJS:.o=.d)
 LIB := animatable_nerf_amd/libaninerf_hip.so
 CXXFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Iinclude
 
-# test-only entries to the training GEMM launchers (tests/csrc/anr_testapi.hip): the library's own objects
-# plus the hooks, loaded by the GEMM kernel tests only
+# test-only entries to the training GEMM launchers (tests/csrc/anr_testapi.hip) and the fused chain programs
+# (tests/csrc/anr_testapi_tchain.hip): the library's own objects plus the hooks, loaded by the kernel tests only
 TESTLIB := tests/libanr_testapi.so
-TESTOBJ := tests/csrc/anr_testapi.o
+TESTOBJ := tests/csrc/anr_testapi.o tests/csrc/anr_testapi_tchain.o
 DEPS += $(TESTOBJ:.o=.d)
 
 all: $(LIB) $(TESTLIB)
@@ -25,7 +25,7 @@ all: $(LIB) $(TESTLIB)
 $(SRC_DIR)/%.o: $(SRC_DIR)/%.hip
 	$(HIPCC) $(CXXFLAGS) -MMD -MP -c $< -o $@
 
-$(TESTOBJ): tests/csrc/anr_testapi.hip
+tests/csrc/%.o: tests/csrc/%.hip
 	$(HIPCC) $(CXXFLAGS) -MMD -MP -c $< -o $@
 
 $(TESTLIB): $(OBJS) $(TESTOBJ)

@@ -216,9 +216,11 @@ struct TcArgs {
   int ld_mem2, kmem2_cols;
   int mem_f32, mem2_f32;  // the memory operands are fp32 rows (else bf16)
   // ReLU mask bits per layer, rows of 32 B (lane h of a sample: 8 B; packed word i = 4 s + j of the epilogue
-  // (neurons 32 s + 8 h + 2 j + {0, 1}) at bits (i & 15) and 16 + (i & 15) of dword i >> 4),
-  // at least ceil(rows / 128) x 128 rows: forward programs write them for their ReLU layers (when set),
-  // backward programs read the mask of each masked layer's outputs
+  // (neurons 32 s + 8 h + 2 j + {0, 1}) at bits (i & 15) and 16 + (i & 15) of dword i >> 4), 8-B aligned:
+  // forward programs write them for their ReLU layers (when set; rows < M only), backward programs read
+  // the mask of each masked layer's outputs. A backward program's mask DMA reads 128 rows from every tile's
+  // first row and tiles are 112 rows apart, so with M rows a buffer it reads holds at least
+  // (ceil(M / 112) - 1) x 112 + 128 rows (M = 128: the second tile reads rows 112..239)
   void* bits[12];
   float* aux;             // backward: the gamma gradient rows (fp32): layer 5 stores (adds when aux_acc), layer 0 adds
   int ld_aux, aux_cols, aux_acc;

@@ -62,7 +62,9 @@ struct TLayout {
 
 // ReLU mask bits of one chain layer (TcArgs::bits): 32 B per sample, 128 rows past the last (a tile's
 // mask DMA reads 4 KiB = 128 rows from the tile's first)
-size_t bits_stride(long N) { return (size_t)((N + 127) / 128 * 128 + 128) * 32; }  // + the last tile's DMA overrun
+// rows of a layer's mask bits: at least TcArgs::bits' (ceil(N / 112) - 1) x 112 + 128 (the last tile's mask
+// DMA reads 128 rows from its first row; N rounded up to 128, + 128, covers it for every N)
+size_t bits_stride(long N) { return (size_t)((N + 127) / 128 * 128 + 128) * 32; }
 
 // f: the frame, for the voxel counts of its pose / T-pose blend-weight volumes
 TLayout tlayout(int n_rays, int chunk, const anr_frame* f) {
