@@ -26,6 +26,7 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_alpha_workspace_bytes', 'anr_alpha_points', 'anr_alpha_counts', 'anr_mc_workspace_bytes',
            'anr_mc_count', 'anr_mc_emit', 'anr_anim_workspace_bytes', 'anr_anim_step',
            'anr_train_ray_workspace_bytes', 'anr_train_ray_lists', 'anr_train_ray_gather',
+           'anr_train_ray_sample',
            'anr_network_workspace_bytes', 'anr_network_fwd', 'anr_network_counts', 'anr_network_bw_rows',
            'anr_network_train_workspace_bytes', 'anr_network_train_fwd', 'anr_network_train_bwd',
            'anr_points_workspace_bytes', 'anr_blend_weights', 'anr_canonical_alpha', 'anr_train_step_hooked',
@@ -262,6 +263,10 @@ def load():
     lib.anr_train_ray_gather.argtypes = [ctypes.c_int, ctypes.c_int, D, D, D, D, ctypes.c_int, P, P, P, ctypes.c_int,
                                          P, P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                          P, P, P, P, P, P, P, P]
+    lib.anr_train_ray_sample.argtypes = [ctypes.c_int, ctypes.c_int, D, D, D, D, ctypes.c_int, P, P, P, P, P, P, P,
+                                         ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
+                                         ctypes.c_uint64, ctypes.c_uint64, P, P, P, P, P, P, P, P, P, P, P]
     lib.anr_alpha_workspace_bytes.restype = ctypes.c_size_t
     lib.anr_alpha_workspace_bytes.argtypes = [ctypes.c_long, ctypes.POINTER(AlphaOpts), ctypes.POINTER(Frame)]
     lib.anr_alpha_points.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(Frame), P, ctypes.c_long,

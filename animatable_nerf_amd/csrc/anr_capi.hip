@@ -389,6 +389,50 @@ int anr_train_ray_gather(int H, int W, const double* Kinv, const double* R, cons
   return check_launch("anr_train_ray_gather");
 }
 
+int anr_train_ray_sample(int H, int W, const double* Kinv, const double* R, const double* T, const double* origin,
+                         int fp64, const float* bounds, const float* img, const uint8_t* bound_mask,
+                         const uint8_t* occ_mask, const int32_t* list_body, const int32_t* list_face,
+                         const int32_t* list_bound, int n_body_px, int n_face_px, int n_bound_px, int mask_bkgd,
+                         double body_ratio, double face_ratio, int nrays, int max_rounds, uint64_t seed, uint64_t step,
+                         float* ray_o, float* ray_d, float* rgb, float* near_, float* far_, int32_t* coord,
+                         uint8_t* mask_at_box, uint8_t* occupancy, int32_t* n_out, int32_t* shortfall, void* stream) {
+  if (H <= 0 || W <= 0 || !Kinv || !R || !T || !origin || !bounds || !img || !bound_mask || !list_bound || !ray_o ||
+      !ray_d || !rgb || !near_ || !far_ || !coord || !mask_at_box || !n_out || !shortfall)
+    return fail(ANR_E_ARG, "anr_train_ray_sample: NULL argument");
+  if ((occ_mask != nullptr) != (occupancy != nullptr))
+    return fail(ANR_E_ARG, "anr_train_ray_sample: occ_mask and occupancy go together (both or neither NULL)");
+  if ((long)H * W > (1L << 29)) return fail(ANR_E_ARG, "anr_train_ray_sample: image too large");
+  if (nrays <= 0 || nrays > 65536) return fail(ANR_E_ARG, "anr_train_ray_sample: nrays must be in 1..65536");
+  if (max_rounds < 1 || max_rounds > 1024) return fail(ANR_E_ARG, "anr_train_ray_sample: max_rounds must be in 1..1024");
+  // negated comparisons: a NaN ratio is rejected too
+  if (!(body_ratio >= 0.0 && body_ratio <= 1.0) || !(face_ratio >= 0.0 && face_ratio <= 1.0) ||
+      !(body_ratio + face_ratio <= 1.0))
+    return fail(ANR_E_ARG, "anr_train_ray_sample: ratios must lie in [0,1] and sum to at most 1");
+  if (n_bound_px <= 0 || n_body_px < 0 || n_face_px < 0 || (n_body_px == 0 && body_ratio > 0.0))
+    return fail(ANR_E_ARG, "anr_train_ray_sample: empty pixel list");
+  if ((n_body_px > 0 && !list_body) || (n_face_px > 0 && !list_face))
+    return fail(ANR_E_ARG, "anr_train_ray_sample: NULL pixel list");
+  TrainSampleArgs s{};
+  TrainRayArgs& a = s.r;
+  a.cam.H = H; a.cam.W = W; a.cam.fp64 = fp64 ? 1 : 0;
+  for (int k = 0; k < 9; ++k) { a.cam.Kinv[k] = Kinv[k]; a.cam.R[k] = R[k]; }
+  for (int k = 0; k < 3; ++k) { a.cam.T[k] = T[k]; a.cam.o[k] = origin[k]; }
+  a.cam.bounds = bounds;
+  a.img = img; a.bound_mask = bound_mask; a.mask_bkgd = mask_bkgd ? 1 : 0;
+  a.cap = nrays; a.n_out = n_out;
+  a.ray_o = ray_o; a.ray_d = ray_d; a.rgb = rgb; a.near_ = near_; a.far_ = far_; a.coord = coord;
+  a.mask_at_box = mask_at_box; a.occ_mask = occ_mask; a.occupancy = occupancy;
+  s.list[0] = list_body; s.list[1] = list_face; s.list[2] = list_bound;
+  s.n_px[0] = n_body_px; s.n_px[1] = n_face_px; s.n_px[2] = n_bound_px;
+  s.body_ratio = body_ratio; s.face_ratio = face_ratio;
+  s.max_rounds = max_rounds;
+  s.key[0] = (uint32_t)seed; s.key[1] = (uint32_t)(seed >> 32);
+  s.step[0] = (uint32_t)step; s.step[1] = (uint32_t)(step >> 32);
+  s.shortfall = shortfall;
+  hipLaunchKernelGGL(k_trl_sample, dim3(1), dim3(1024), 0, (hipStream_t)stream, s);
+  return check_launch("anr_train_ray_sample");
+}
+
 size_t anr_params_packed_bytes(void) { return (size_t)packed_bytes_all(); }
 
 int anr_params_pack(const anr_params* p, void* packed, void* stream) {

@@ -83,6 +83,23 @@ struct TrainRayArgs {
   int* n_out;                     // device: rays so far (in/out)
   float *ray_o, *ray_d, *rgb, *near_, *far_;
   int* coord;
+  // written per hit by k_trl_sample only (NULL in k_trl_gather's calls)
+  uint8_t* mask_at_box;           // (cap) 1 per hit
+  const uint8_t* occ_mask;        // (H*W) u8 or NULL
+  uint8_t* occupancy;             // (cap) occ_mask at the hit's pixel
+};
+
+// anr_train_ray_sample: the whole sampling loop in one launch (k_trl_sample). r carries the camera,
+// image, masks and outputs (r.lists / r.draws / r.n_seg unused: the lists are the trimmed ones below
+// and the draws come from Philox4x32-10 under key `key`, counter (slot >> 2, round, step))
+struct TrainSampleArgs {
+  TrainRayArgs r;                 // r.cap = nrays
+  const int* list[3];             // body, face, bound pixel ids
+  int n_px[3];                    // their lengths
+  double body_ratio, face_ratio;
+  int max_rounds;
+  uint32_t key[2], step[2];       // seed, step as (lo, hi)
+  int* shortfall;                 // device: += nrays - *n_out
 };
 
 struct CompositeArgs {
@@ -200,6 +217,7 @@ __global__ void k_cam_scatter(CamArgs a);
 __global__ void k_trl_count(TrainRayArgs a);
 __global__ void k_trl_scatter(TrainRayArgs a);
 __global__ void k_trl_gather(TrainRayArgs a);
+__global__ void k_trl_sample(TrainSampleArgs s);
 __global__ void k_frontend(FrontArgs a);
 __global__ void k_frontend_pts(FrontArgs a);
 __global__ void k_count(CompactArgs a);

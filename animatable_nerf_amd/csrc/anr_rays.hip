@@ -162,8 +162,9 @@ __global__ __launch_bounds__(256) void k_cam_scatter(CamArgs a) {
 // (f) train-split ray sampler: sample_ray_h36m(split='train') (if_nerf_data_utils.py:198-283).
 // The pixel lists np.argwhere(msk == 1), (msk == 13) and (bound_mask == 1) (:238-249), row-major
 // like argwhere, with msk = msk * bound_mask (u8, wrapping) and bound_mask[msk == 100] = 0
-// (:230-231); the random draws into them stay on the host (np.random, so the stream of draws is
-// the reference's), then k_trl_gather turns one round of draws into rays.
+// (:230-231). Two ways on from the lists: the random draws into them stay on the host (np.random,
+// so the stream of draws is the reference's) and k_trl_gather turns one round of draws into rays;
+// or k_trl_sample runs every round itself with counter-based draws (no host in the loop).
 // ------------------------------------------------------------------------------------------
 __device__ __forceinline__ void trl_flags(const TrainRayArgs& a, int pix, int f[3]) {
   const int P = a.cam.H * a.cam.W;
@@ -202,65 +203,149 @@ __global__ __launch_bounds__(256) void k_trl_scatter(TrainRayArgs a) {
   }
 }
 
-// One round of the sampling loop (:236-271): draws[i] indexes list 0 for i < n_seg[0], list 1 for
-// the next n_seg[1], list 2 for the rest (the reference's concatenation order). Per draw: get_rays
-// at the pixel, get_near_far on get_rays' arrays (float64 for a float64 camera), rgb = img (zero
-// outside the bound mask when mask_bkgd, :228); the hits are appended in draw order at *n_out.
-// One 1024-thread workgroup (a round draws at most nrays).
+// One draw of the sampling loop (:236-271), for all 1024 threads of the workgroup at once (call it
+// from uniform control flow: it holds barriers). A live thread brings pixel `pix`: get_rays at the
+// pixel, get_near_far on get_rays' arrays (float64 for a float64 camera), rgb = img (zero outside
+// the bound mask when mask_bkgd, :228). The hits are appended in thread order at `base` (LDS, the
+// rays so far), which is advanced by their number; wsum is LDS scratch of 16 ints.
+__device__ __forceinline__ void trl_draw(const TrainRayArgs& a, bool live, int pix, int* wsum, int& base) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int hit = 0;
+  float d32[3] = {0.f, 0.f, 0.f}, nr = 0.f, fr = 0.f;
+  if (live) {
+    const int r = pix / a.cam.W, c = pix - r * a.cam.W;
+    double d64[3];
+    cam_ray(a.cam, r, c, d32, d64);
+    uint8_t h;
+    if (a.cam.fp64) {
+      near_far_one<double>(a.cam.o, d64, a.cam.bounds, h, nr, fr);
+    } else {
+      const float o32[3] = {(float)a.cam.o[0], (float)a.cam.o[1], (float)a.cam.o[2]};
+      near_far_one<float>(o32, d32, a.cam.bounds, h, nr, fr);
+    }
+    hit = h;
+  }
+  // block-wide exclusive scan of the hit flags (16 waves)
+  const uint64_t bal = __ballot(hit);
+  const int before = __popcll(bal & ((1ull << lane) - 1));
+  if (lane == 0) wsum[w] = __popcll(bal);
+  __syncthreads();
+  int off = base, tot = 0;
+  for (int k = 0; k < 16; ++k) {
+    if (k < w) off += wsum[k];
+    tot += wsum[k];
+  }
+  const int pos = off + before;
+  if (hit && pos < a.cap) {
+    for (int k = 0; k < 3; ++k) {
+      a.ray_o[3 * (size_t)pos + k] = (float)a.cam.o[k];
+      a.ray_d[3 * (size_t)pos + k] = d32[k];
+      a.rgb[3 * (size_t)pos + k] = (a.mask_bkgd && a.bound_mask[pix] != 1) ? 0.0f : a.img[3 * (size_t)pix + k];
+    }
+    a.near_[pos] = nr;
+    a.far_[pos] = fr;
+    a.coord[2 * (size_t)pos] = pix / a.cam.W;
+    a.coord[2 * (size_t)pos + 1] = pix % a.cam.W;
+    if (a.mask_at_box) a.mask_at_box[pos] = 1;
+    if (a.occ_mask) a.occupancy[pos] = a.occ_mask[pix];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) base += tot;
+  __syncthreads();
+}
+
+// One round of the sampling loop with the caller's draws: draws[i] indexes list 0 for i < n_seg[0],
+// list 1 for the next n_seg[1], list 2 for the rest (the reference's concatenation order); the hits
+// are appended in draw order at *n_out. One 1024-thread workgroup (a round draws at most nrays).
 __global__ __launch_bounds__(1024) void k_trl_gather(TrainRayArgs a) {
   __shared__ int wsum[16];
   __shared__ int base;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   if (threadIdx.x == 0) base = *a.n_out;
   __syncthreads();
   const size_t P = (size_t)a.cam.H * a.cam.W;
   const int n = a.n_seg[0] + a.n_seg[1] + a.n_seg[2];
   for (int i0 = 0; i0 < n; i0 += 1024) {
     const int i = i0 + threadIdx.x;
-    int hit = 0, pix = 0;
-    float d32[3] = {0.f, 0.f, 0.f}, nr = 0.f, fr = 0.f;
+    int pix = 0;
     if (i < n) {
       const int seg = i < a.n_seg[0] ? 0 : (i < a.n_seg[0] + a.n_seg[1] ? 1 : 2);
       pix = a.lists[seg * P + a.draws[i]];
-      const int r = pix / a.cam.W, c = pix - r * a.cam.W;
-      double d64[3];
-      cam_ray(a.cam, r, c, d32, d64);
-      uint8_t h;
-      if (a.cam.fp64) {
-        near_far_one<double>(a.cam.o, d64, a.cam.bounds, h, nr, fr);
-      } else {
-        const float o32[3] = {(float)a.cam.o[0], (float)a.cam.o[1], (float)a.cam.o[2]};
-        near_far_one<float>(o32, d32, a.cam.bounds, h, nr, fr);
-      }
-      hit = h;
     }
-    // block-wide exclusive scan of the hit flags (16 waves)
-    const uint64_t bal = __ballot(hit);
-    const int before = __popcll(bal & ((1ull << lane) - 1));
-    if (lane == 0) wsum[w] = __popcll(bal);
-    __syncthreads();
-    int off = base, tot = 0;
-    for (int k = 0; k < 16; ++k) {
-      if (k < w) off += wsum[k];
-      tot += wsum[k];
-    }
-    const int pos = off + before;
-    if (hit && pos < a.cap) {
-      for (int k = 0; k < 3; ++k) {
-        a.ray_o[3 * (size_t)pos + k] = (float)a.cam.o[k];
-        a.ray_d[3 * (size_t)pos + k] = d32[k];
-        a.rgb[3 * (size_t)pos + k] = (a.mask_bkgd && a.bound_mask[pix] != 1) ? 0.0f : a.img[3 * (size_t)pix + k];
-      }
-      a.near_[pos] = nr;
-      a.far_[pos] = fr;
-      a.coord[2 * (size_t)pos] = pix / a.cam.W;
-      a.coord[2 * (size_t)pos + 1] = pix % a.cam.W;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) base += tot;
-    __syncthreads();
+    trl_draw(a, i < n, pix, wsum, base);
   }
   if (threadIdx.x == 0) *a.n_out = base;
+}
+
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): counter c, key k -> 4 words in c
+__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int round = 0; round < 10; ++round) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
+    c[0] = n0;
+    c[1] = (uint32_t)p1;
+    c[2] = n2;
+    c[3] = (uint32_t)p0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+}
+
+// The whole sampling loop (:236-271) in one launch of one 1024-thread workgroup: every round sizes
+// its three segments from the rays still missing, as the reference does, draws slot i of round r as
+// word i & 3 of Philox4x32-10 at counter (i >> 2, r, step) under key seed, index = (x * n_list) >> 32,
+// and runs trl_draw on it. Ends when nrays rays are in or after max_rounds rounds (the reference's
+// loop is unbounded); then rows >= n_out become masked-out rays (mask_at_box 0) and shortfall grows
+// by their number. Every loop condition is a kernel argument or `base` read behind a barrier, so
+// uniform over the workgroup.
+__global__ __launch_bounds__(1024) void k_trl_sample(TrainSampleArgs s) {
+  __shared__ int wsum[16];
+  __shared__ int base;
+  const TrainRayArgs& a = s.r;
+  const int nrays = a.cap;
+  if (threadIdx.x == 0) base = 0;
+  __syncthreads();
+  for (int round = 0; round < s.max_rounds; ++round) {
+    const int done = base;  // trl_draw leaves a barrier behind its last write of base
+    if (done >= nrays) break;
+    const int rem = nrays - done;
+    // int(rem * ratio) of the reference: a double product, truncated
+    const int n_body = (int)((double)rem * s.body_ratio);
+    const int n_face_formula = (int)((double)rem * s.face_ratio);
+    const int n_rand = rem - n_body - n_face_formula;  // the formula value also when the face list is empty
+    const int n_face = s.n_px[1] > 0 ? n_face_formula : 0;  // no face list: body and random draws only
+    const int n = n_body + n_face + n_rand;
+    for (int i0 = 0; i0 < n; i0 += 1024) {
+      const int i = i0 + threadIdx.x;
+      int pix = 0;
+      if (i < n) {
+        const int seg = i < n_body ? 0 : (i < n_body + n_face ? 1 : 2);
+        uint32_t c[4] = {(uint32_t)i >> 2, (uint32_t)round, s.step[0], s.step[1]};
+        philox4x32_10(c, s.key[0], s.key[1]);
+        const uint32_t x = c[i & 3];
+        pix = s.list[seg][(uint32_t)(((uint64_t)x * (uint32_t)s.n_px[seg]) >> 32)];
+      }
+      trl_draw(a, i < n, pix, wsum, base);
+    }
+  }
+  const int n_out = base;
+  for (int pos = n_out + threadIdx.x; pos < nrays; pos += 1024) {
+    for (int k = 0; k < 3; ++k) {
+      a.ray_o[3 * (size_t)pos + k] = (float)a.cam.o[k];
+      a.ray_d[3 * (size_t)pos + k] = k == 2 ? 1.0f : 0.0f;
+      a.rgb[3 * (size_t)pos + k] = 0.0f;
+    }
+    a.near_[pos] = 0.0f;
+    a.far_[pos] = 0.0f;
+    a.coord[2 * (size_t)pos] = 0;
+    a.coord[2 * (size_t)pos + 1] = 0;
+    a.mask_at_box[pos] = 0;
+    if (a.occ_mask) a.occupancy[pos] = 0;
+  }
+  if (threadIdx.x == 0) {
+    *a.n_out = n_out;
+    if (n_out < nrays) atomicAdd(s.shortfall, nrays - n_out);
+  }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -4,6 +4,8 @@
 * train split: ``sample_ray_h36m(split='train')`` (:198-283) through ``anr_train_ray_lists`` /
   ``anr_train_ray_gather``: the pixel lists, rays, float64 box test, rgb gather and hit compaction
   run on the GPU; the np.random draws stay on the host so the random stream is the reference's.
+  ``ResidentViews`` keeps a view's image, masks and pixel lists in HBM and draws a whole batch in one
+  launch (``anr_train_ray_sample``: counter-based draws, no host in the loop).
 
 The 3x3 inverse of K and the camera origin -R^T T are formed with numpy on the host exactly as the
 reference does. ``get_bound_2d_mask`` (:114-136) is per-frame host work like the reference's; it
@@ -172,6 +174,130 @@ def sample_ray_h36m(img, msk, K, R, T, bounds, nrays, split, mask_bkgd=True, bod
         nsampled = int(n_out.item())
     mask_at_box = torch.ones(nrays, dtype=torch.bool, device=dev)
     return rgb, ray_o, ray_d, near, far, coord, mask_at_box
+
+
+class ResidentViews:
+    """Training views kept resident in HBM, and the train-split batch drawn from them on the device.
+
+    ``sample_ray_h36m(split='train')`` uploads the image and masks, rebuilds the pixel lists, reads
+    their counts back, draws with np.random on the host and reads ``n_out`` once per resampling round:
+    host round trips in front of every training step. Here ``add`` does the per-view work once (upload,
+    ``anr_train_ray_lists``, one read of the counts) and ``sample`` is one ``anr_train_ray_sample``
+    launch that runs the whole loop of if_nerf_data_utils.py:236-271 on the device with counter-based
+    draws (Philox4x32-10 keyed by ``seed``, counted by ``step``, the round and the slot; see
+    include/aninerf.h): no host sync, no H2D copy, no host RNG between two steps. The rays are NOT the
+    ones np.random would draw; they are the same function of (seed, step) on every run.
+
+    Multi-rank training: every rank must draw different rays, so the caller folds its rank into
+    ``seed`` (e.g. ``seed = base_seed * world_size + rank``); ``step`` is the global iteration.
+
+    A batch can fall short of ``nrays`` only when ``max_rounds`` rounds did not find enough rays that
+    hit the box; the missing rows are rays with ``mask_at_box == 0`` (the training losses skip them)
+    and are counted in ``shortfall()``."""
+
+    VOLATILE = ('rgb', 'ray_o', 'ray_d', 'near', 'far', 'mask_at_box', 'coord', 'occupancy')
+
+    def __init__(self, device='cuda', nrays=1024, seed=0, mask_bkgd=True, body_sample_ratio=0.5,
+                 face_sample_ratio=0.0, max_rounds=64):
+        self.lib = _lib.load()
+        self.device = dev = torch.device(device)
+        self.nrays, self.seed, self.max_rounds = int(nrays), int(seed), int(max_rounds)
+        self.mask_bkgd = bool(mask_bkgd)
+        self.body_ratio, self.face_ratio = float(body_sample_ratio), float(face_sample_ratio)
+        if not 1 <= self.nrays <= 65536:
+            raise ValueError(f'ResidentViews: nrays must be in 1..65536, got {nrays}')
+        if not 1 <= self.max_rounds <= 1024:
+            raise ValueError(f'ResidentViews: max_rounds must be in 1..1024, got {max_rounds}')
+        if not (0.0 <= self.body_ratio <= 1.0 and 0.0 <= self.face_ratio <= 1.0
+                and self.body_ratio + self.face_ratio <= 1.0):
+            raise ValueError('ResidentViews: the sample ratios must lie in [0,1] and sum to at most 1')
+        R = self.nrays
+        self._out = {'rgb': torch.zeros((1, R, 3), device=dev), 'ray_o': torch.zeros((1, R, 3), device=dev),
+                     'ray_d': torch.zeros((1, R, 3), device=dev), 'near': torch.zeros((1, R), device=dev),
+                     'far': torch.zeros((1, R), device=dev),
+                     'mask_at_box': torch.zeros((1, R), dtype=torch.uint8, device=dev),
+                     'coord': torch.zeros((1, R, 2), dtype=torch.int32, device=dev)}
+        self._occupancy = torch.zeros((1, R), dtype=torch.uint8, device=dev)
+        self.n_out = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._shortfall = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._views = {}
+
+    def add(self, key, img, msk, K, R, T, bounds, bound_mask=None, orig_msk=None):
+        """Make view ``key`` resident (one-time work per (frame, view); synchronises once). Arguments as
+        ``sample_ray_h36m``; ``orig_msk`` is the occupancy mask of tpose_dataset.py:229-233, already
+        through ``crop_mask_edge`` where the caller applies it. ValueError where no batch could be
+        drawn: an empty bound list, or an empty body list with a body ratio above 0."""
+        dev = self.device
+        H, W = img.shape[:2]
+        if bound_mask is None:
+            pose = np.concatenate([np.asarray(R), np.asarray(T).reshape(3, 1)], axis=1)
+            bound_mask = get_bound_2d_mask(bounds, K, pose, H, W)
+        v = {'H': H, 'W': W}
+        v['cam'] = _camera(K, R, T)
+        v['bounds'] = torch.as_tensor(np.asarray(bounds, dtype=np.float32).reshape(2, 3)).to(dev)
+        v['img'] = torch.as_tensor(np.ascontiguousarray(img, dtype=np.float32)).to(dev)
+        v['bm'] = torch.as_tensor(np.ascontiguousarray(bound_mask, dtype=np.uint8)).to(dev)
+        v['occ'] = None
+        if orig_msk is not None:
+            if tuple(np.shape(orig_msk)) != (H, W):
+                raise ValueError(f'ResidentViews.add: orig_msk {np.shape(orig_msk)} is not the image size {(H, W)}')
+            v['occ'] = torch.as_tensor(np.ascontiguousarray(orig_msk, dtype=np.uint8)).to(dev)
+        msk_d = torch.as_tensor(np.ascontiguousarray(msk, dtype=np.uint8)).to(dev)
+        P = H * W
+        lists = torch.empty(3 * P, dtype=torch.int32, device=dev)
+        counts = torch.zeros(3, dtype=torch.int32, device=dev)
+        ws_bytes = self.lib.anr_train_ray_workspace_bytes(H, W)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(self.lib.anr_train_ray_lists(H, W, _lib.ptr(msk_d), _lib.ptr(v['bm']), _lib.ptr(lists),
+                                                _lib.ptr(counts), _lib.ptr(ws), ws_bytes, _lib.stream_ptr(dev)),
+                   'anr_train_ray_lists')
+        n = [int(c) for c in counts.cpu()]
+        if n[2] <= 0:
+            raise ValueError(f'ResidentViews.add({key!r}): no pixel in the bound mask')
+        if n[0] <= 0 and self.body_ratio > 0:
+            raise ValueError(f'ResidentViews.add({key!r}): no body pixel (msk == 1) with body_sample_ratio > 0')
+        v['n'] = n
+        v['lists'] = [lists[k * P:k * P + n[k]].clone() for k in range(3)]  # the used prefixes only
+        Kinv, Rd, Td, o, fp64 = v['cam']
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+        lp = lambda t: _lib.ptr(t) if t.numel() else None
+        has_occ = v['occ'] is not None
+        # everything of the call but (seed, step, stream)
+        v['head'] = (H, W, dp(Kinv), dp(Rd), dp(Td), dp(o), 1 if fp64 else 0, _lib.ptr(v['bounds']), _lib.ptr(v['img']),
+                     _lib.ptr(v['bm']), _lib.ptr(v['occ']) if has_occ else None, lp(v['lists'][0]), lp(v['lists'][1]),
+                     lp(v['lists'][2]), n[0], n[1], n[2], 1 if self.mask_bkgd else 0, self.body_ratio, self.face_ratio,
+                     self.nrays, self.max_rounds)
+        out = self._out
+        v['tail'] = tuple(_lib.ptr(out[k]) for k in ('ray_o', 'ray_d', 'rgb', 'near', 'far', 'coord', 'mask_at_box')) + (
+            _lib.ptr(self._occupancy) if has_occ else None, _lib.ptr(self.n_out), _lib.ptr(self._shortfall))
+        self._views[key] = v
+
+    def sample(self, key, step):
+        """One launch: the batch of view ``key`` at iteration ``step`` written into the object's fixed
+        buffers. -> dict of ``rgb, ray_o, ray_d (1,R,3)``, ``near, far (1,R)`` float32, ``mask_at_box
+        (1,R)`` uint8, ``coord (1,R,2)`` int32, ``occupancy (1,R)`` uint8 when the view has ``orig_msk``
+        — the same tensor objects on every call, valid until the next ``sample`` — and
+        ``'anr_volatile'``, the names of those keys: they are rewritten in place without a bump of
+        their version counters, so whoever caches copies by version (FusedStep) must copy them anew."""
+        v = self._views[key]
+        _lib.check(self.lib.anr_train_ray_sample(*v['head'], self.seed & 0xFFFFFFFFFFFFFFFF,
+                                                 int(step) & 0xFFFFFFFFFFFFFFFF, *v['tail'],
+                                                 _lib.stream_ptr(self.device)), 'anr_train_ray_sample')
+        out = dict(self._out)
+        if v['occ'] is not None:
+            out['occupancy'] = self._occupancy
+        out['anr_volatile'] = tuple(k for k in self.VOLATILE if k in out)
+        return out
+
+    def shortfall(self):
+        """Rays missing from all batches so far (reads the device counter: the one synchronising call,
+        meant for once per epoch)."""
+        return int(self._shortfall.item())
+
+    def resident_bytes(self):
+        ts = [t for v in self._views.values() for t in [v['img'], v['bm'], v['bounds'], v['occ']] + v['lists']
+              if t is not None]
+        return sum(t.numel() * t.element_size() for t in ts)
 
 
 class ResidentFrames:

@@ -213,7 +213,8 @@ class FusedStep:
         consecutive steps call anr_train_step_hooked with identical arguments: from the second such
         call on, the library replays the step as one captured graph. A buffer is rebuilt when a
         shape changes; a source tensor unchanged since the last copy (same storage and version
-        counter, e.g. a frame's resident volumes) is not copied again."""
+        counter, e.g. a frame's resident volumes) is not copied again, unless the batch names it in
+        'anr_volatile'."""
         dev = self.flat.device
         R = batch['ray_o'].shape[1]
         ns = int(self.cfg.N_samples)
@@ -230,12 +231,17 @@ class FusedStep:
             st = self._st = {'shapes': shapes, 'batch': sb, 'src': {}, 't_rand': torch.empty((R, ns), device=dev)}
             st['call'] = _Call(self.renderer, sb, st['t_rand'])
         sb, src = st['batch'], st['src']
+        # keys the batch's producer rewrites in place through the library (data.ResidentViews.sample):
+        # such writes bump no version counter, so these are copied every step
+        volatile = batch.get('anr_volatile', ())
         for k in self._STATIC_KEYS:
             v = batch[k]
             tag = (v.data_ptr(), v._version, v.device)
-            if src.get(k) != tag:
+            if k in volatile or src.get(k, (None,))[0] != tag:
                 sb[k].copy_(v)
-                src[k] = tag
+                # the source stays referenced until another replaces it: a freed batch's address (and a fresh
+                # tensor's version 0) would otherwise come back with the next batch and skip its copy
+                src[k] = (tag, v)
         if t_rand is not None:
             st['t_rand'].copy_(t_rand.reshape(R, ns))
         elif self.cfg.perturb > 0:

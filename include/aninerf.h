@@ -185,6 +185,40 @@ int anr_train_ray_gather(int H, int W, const double* Kinv, const double* R, cons
                          float* ray_o, float* ray_d, float* rgb, float* near_, float* far_, int32_t* coord,
                          int32_t* n_out, void* stream);
 
+/* ---- (f) train-split ray sampler, whole loop on the device -------------------------------------
+ * anr_train_ray_sample replaces the loop `while nsampled < nrays` of sample_ray_h36m(split='train')
+ * (if_nerf_data_utils.py:236-271) and the occupancy lookup of tpose_dataset.py:233 with ONE launch
+ * of one 1024-thread workgroup: no host sync, no host RNG, no H2D copy between training steps.
+ *  Inputs (device unless said): camera arguments as anr_camera_rays; img (H*W,3) f32; bound_mask
+ *    (H*W) u8, the one anr_train_ray_lists saw; occ_mask (H*W) u8 or NULL; list_body / list_face /
+ *    list_bound = the used prefixes of anr_train_ray_lists' three lists, their lengths n_body_px /
+ *    n_face_px / n_bound_px by value (an empty list may be NULL).
+ *  Per round, with rem = nrays - (rays so far): n_body = (int)((double)rem * body_ratio), n_face =
+ *    (int)((double)rem * face_ratio), n_rand = rem - n_body - n_face. An empty face list
+ *    gets no slots but n_rand keeps the subtraction above (the reference then concatenates body and
+ *    random draws only). Slots i = 0.. run over [body, face, rand]; slot i of round r draws
+ *        x = word (i & 3) of Philox4x32-10(counter = (i >> 2, r, step_lo, step_hi), key = (seed_lo, seed_hi))
+ *        index = ((uint64)x * n_list) >> 32
+ *    which is uniform over the slot's list up to a relative bias of at most n_list / 2^32. Per slot
+ *    the work is anr_train_ray_gather's (get_rays, box test in the camera's precision, rgb with the
+ *    mask_bkgd zeroing), hits appended in slot order.
+ *  Ends when nrays rays are in, or after max_rounds rounds (1..1024; the reference's loop is
+ *    unbounded). *n_out (device int32) = rays sampled. Rows >= n_out are filled as rays the training
+ *    losses skip: mask_at_box 0, ray_o = origin, ray_d = (0,0,1), near = far = 0, rgb = 0, coord = 0,
+ *    occupancy = 0; *shortfall (device int32, accumulating: zero it once) += nrays - n_out.
+ *  Outputs: ray_o/ray_d/rgb (nrays,3) f32, near/far (nrays) f32, coord (nrays,2) int32 (row, col),
+ *    mask_at_box (nrays) u8, occupancy (nrays) u8 (NULL exactly when occ_mask is).
+ *  ANR_E_ARG before any HIP call for: a NULL pointer, nrays outside 1..65536, max_rounds outside
+ *    1..1024, a ratio outside [0,1] or body_ratio + face_ratio > 1, n_bound_px <= 0, n_body_px <= 0
+ *    with body_ratio > 0. Multi-process training: fold the rank into seed. */
+int anr_train_ray_sample(int H, int W, const double* Kinv, const double* R, const double* T, const double* origin,
+                         int fp64, const float* bounds, const float* img, const uint8_t* bound_mask,
+                         const uint8_t* occ_mask, const int32_t* list_body, const int32_t* list_face,
+                         const int32_t* list_bound, int n_body_px, int n_face_px, int n_bound_px, int mask_bkgd,
+                         double body_ratio, double face_ratio, int nrays, int max_rounds, uint64_t seed, uint64_t step,
+                         float* ray_o, float* ray_d, float* rgb, float* near_, float* far_, int32_t* coord,
+                         uint8_t* mask_at_box, uint8_t* occupancy, int32_t* n_out, int32_t* shortfall, void* stream);
+
 /* ---- weights --------------------------------------------------------------------------- */
 size_t anr_params_packed_bytes(void);
 int anr_params_pack(const anr_params* p, void* packed, void* stream);
