@@ -153,12 +153,23 @@ __global__ void k_st_outer_add(const float* __restrict__ bsum, const float* __re
   if (o < nout && q < nq) dW[(long)o * in_ch + col0 + q] += bsum[o] * v[q];
 }
 
-// dst[c] += sum over n rows of H[r][c] (c < 256): the tangent output adjoint e0 of lin8 (row 0 of dW8)
-__global__ void k_st_colsum(const float* __restrict__ H, long ldh, int n, float* dst) {
+// dst[c] += sum over n rows of H[r][c] (c < 256): the tangent output adjoint e0 of lin8 (row 0 of dW8).
+// part != NULL (deterministic mode): the block's sums go to part[block][256] instead of the atomics and
+// k_st_colsum_det adds them in block order
+__global__ void k_st_colsum(const float* __restrict__ H, long ldh, int n, float* dst, float* part) {
   const int c = threadIdx.x;
   float acc = 0.f;
   for (int r = blockIdx.x; r < n; r += gridDim.x) acc += H[(long)r * ldh + c];
-  atomicAdd(dst + c, acc);
+  if (part) part[(long)blockIdx.x * 256 + c] = acc;
+  else atomicAdd(dst + c, acc);
+}
+
+// dst[c] += part[0][c] + part[1][c] + .. + part[nb - 1][c] in that order (one thread per column, one launch)
+__global__ __launch_bounds__(256) void k_st_colsum_det(const float* __restrict__ part, int nb, float* dst) {
+  const int c = threadIdx.x;
+  float t = 0.f;
+  for (int b = 0; b < nb; ++b) t += part[(long)b * 256 + c];
+  dst[c] += t;
 }
 
 // weight norm backward (torch._weight_norm, dim 0): W = g v / |v|_row; from dW (effective):
@@ -205,6 +216,7 @@ struct StRaw {
   float* dYc;           // [n][4]
   float* ds;            // [n]
   float* dbeta;         // device scalar (atomic)
+  float* dbeta_part;    // deterministic mode: per-block partials [grid] (k_det_sum adds them), NULL: the atomic
 };
 
 // raw = (sigmoid(yc), 1 - exp(-relu(sigma(s, beta)) 0.005)), zero outside the widened tbounds
@@ -254,7 +266,11 @@ __global__ __launch_bounds__(256) void k_st_raw_bwd(StRaw a) {
   for (int off = 32; off > 0; off >>= 1) db += __shfl_xor(db, off);
   if ((threadIdx.x & 63) == 0) sb[threadIdx.x >> 6] = db;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(a.dbeta, sb[0] + sb[1] + sb[2] + sb[3]);
+  if (threadIdx.x == 0) {
+    const float t = sb[0] + sb[1] + sb[2] + sb[3];
+    if (a.dbeta_part) a.dbeta_part[blockIdx.x] = t;
+    else atomicAdd(a.dbeta, t);
+  }
 }
 
 // loss accumulators (acc): 0 offset |r| sum, 1 eikonal sum, 2 observed-eikonal sum, 3 BCE sum,
@@ -269,15 +285,23 @@ struct StLoss {
   float* dG;           // [n][4] out: normal adjoint (colour + eikonal)
   float* dZ8;          // [n][264] col 0 out: sdf adjoint
   float* acc;
+  float* part;         // deterministic mode: per-block partials [2][part_ld] (offset, eikonal), NULL: atomics
+  int part_ld;
 };
 
-__device__ __forceinline__ void block_add(float v, float* dst) {
+// the block's sum of v into *dst (atomic), or, part != NULL (deterministic mode), stored to part[block] for
+// k_det_sum to add in block order; the order inside a block is fixed either way
+__device__ __forceinline__ void block_add(float v, float* dst, float* part) {
   __shared__ float sb[4];
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
   __syncthreads();
   if ((threadIdx.x & 63) == 0) sb[threadIdx.x >> 6] = v;
   __syncthreads();
-  if (threadIdx.x == 0) atomicAdd(dst, sb[0] + sb[1] + sb[2] + sb[3]);
+  if (threadIdx.x == 0) {
+    const float t = sb[0] + sb[1] + sb[2] + sb[3];
+    if (part) part[blockIdx.x] = t;
+    else atomicAdd(dst, t);
+  }
 }
 
 // offset_loss = mean |resd|, grad_loss = mean (|g| - 1)^2 (tpose_trainer.py:26-36) and their adjoints
@@ -302,12 +326,13 @@ __global__ __launch_bounds__(256) void k_st_sample_loss(StLoss a) {
     a.dG[(size_t)i * 4 + 3] = 0.f;
     a.dZ8[(size_t)i * 264] = a.ds[i];
   }
-  block_add(lo, a.acc + 0);
-  block_add(lg, a.acc + 1);
+  block_add(lo, a.acc + 0, a.part);
+  block_add(lg, a.acc + 1, a.part ? a.part + a.part_ld : nullptr);
 }
 
 // observed gradients: ograd_loss = mean (|og| - 1)^2 and its adjoint dog (tpose_trainer.py:38-43)
-__global__ __launch_bounds__(256) void k_st_obs_loss(const float* __restrict__ og, int n_o, float* dog, float* acc) {
+__global__ __launch_bounds__(256) void k_st_obs_loss(const float* __restrict__ og, int n_o, float* dog, float* acc,
+                                                     float* part) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   float l = 0.f;
   if (i < n_o) {
@@ -318,11 +343,13 @@ __global__ __launch_bounds__(256) void k_st_obs_loss(const float* __restrict__ o
     for (int c = 0; c < 3; ++c) dog[(size_t)i * 4 + c] = g[c] * sg;
     dog[(size_t)i * 4 + 3] = 0.f;
   }
-  block_add(l, acc + 2);
+  block_add(l, acc + 2, part);
 }
 
 // msk_sdf (tpose_renderer.py:134-152): per ray the min sdf over its 64 samples and the first sample
 // holding it (torch.min's index), the intersection test, the list an entry goes to; count entries
+// (acc[6] counts in steps of 1.f: exact and order-independent below 2^24, and a call has at most 2^18 rays
+// (check_train), so this atomic stays in the deterministic mode)
 __global__ __launch_bounds__(256) void k_st_msk_rays(const float* __restrict__ sdf, const uint8_t* __restrict__ occ,
                                                      int R, float* mn_out, int* am_out, uint8_t* flags, float* acc) {
   const int lane = threadIdx.x & 63;
@@ -349,7 +376,7 @@ __global__ __launch_bounds__(256) void k_st_msk_rays(const float* __restrict__ s
 // to the argmin sample's sdf when that sample was kept (dropped samples hold the constant 10)
 __global__ __launch_bounds__(256) void k_st_msk_loss(const float* __restrict__ mn, const int* __restrict__ am,
                                                      const uint8_t* __restrict__ flags, const int* __restrict__ inv,
-                                                     int R, float alpha, float* ds, float* acc) {
+                                                     int R, float alpha, float* ds, float* acc, float* part) {
   const int ray = blockIdx.x * blockDim.x + threadIdx.x;
   float l = 0.f;
   if (ray < R && flags[ray]) {
@@ -361,7 +388,7 @@ __global__ __launch_bounds__(256) void k_st_msk_loss(const float* __restrict__ m
     const int i = inv[am[ray]];
     if (i >= 0) ds[i] += -(sg - y) / L;
   }
-  block_add(l, acc + 3);
+  block_add(l, acc + 3, part);
 }
 
 // loss vector (include/aninerf.h anr_sdf_train_step)
@@ -637,6 +664,12 @@ struct TG {
   ~TG() { plan_end(); }
   int lg32 = 0;  // exact fp32 products on k_lgemm's F32 kernels (resident fp32 weight image) where they fit
   int wg32 = 0;  // exact fp32 weight gradients on k_wgrad_f32 (slab + reduce) where they fit
+  // deterministic mode (train_det(), read once per call): the slab reductions in fixed order
+  // (k_wgrad_reduce_det), the generic split-K products through per-split partials in det_scratch
+  // (launch_gemm_det); products that share a dW / bsum are separate calls, so consecutive launches on s
+  bool det = false;
+  float* det_scratch = nullptr;
+  size_t det_floats = 0;
   int run(GemmArgs g, int M) {
     if (M <= 0 || g.N <= 0) return ANR_OK;
     g.M = M;
@@ -682,7 +715,7 @@ struct TG {
       w.x3 = 1;
       w.dY = dY; w.ldY = ldY; w.nout = Nout; w.X = X; w.ldX = ldX; w.K = K;
       w.dW = dW + c0; w.ldw = in_ch; w.bsum = bsum; w.slab = slab;
-      if (launch_wgrad(w, M, s) != 0) return check_launch("k_wgrad (sdf train)");
+      if (launch_wgrad(w, M, s, det) != 0) return check_launch("k_wgrad (sdf train)");
       return ANR_OK;
     }
     if (!wg_x3 && wg32 && slab) {
@@ -708,7 +741,7 @@ struct TG {
             w.dW = dW + cs + (long)r0 * in_ch + k0;
             w.bsum = bsum && k0 == 0 ? bsum + r0 : nullptr;
             if (pass == 0) fits = wgrad_f32_fits(w);
-            else if (launch_wgrad_f32(w, M, s) != 0) return check_launch("k_wgrad_f32 (sdf train)");
+            else if (launch_wgrad_f32(w, M, s, det) != 0) return check_launch("k_wgrad_f32 (sdf train)");
           }
       if (fits) return ANR_OK;
     }
@@ -719,6 +752,12 @@ struct TG {
     g.seg[0] = GemmSeg{dY, 1, ldY, X, ldX, 1, M};
     g.C = dW + c0; g.ldc = in_ch; g.atomic = 1;
     g.ksplit = (M + 511) / 512;
+    if (det) {  // 512-sample splits, every one live (M is the host's count), summed in split order
+      g.kper = 512;
+      if (launch_gemm_det(g, Nout, det_scratch, det_floats, s) != 0)
+        return fail(ANR_E_WORKSPACE, "sdf train: deterministic weight gradient without scratch");
+      return check_launch("k_gemm (sdf train, deterministic split-K)");
+    }
     return run(g, Nout);
   }
   // dX[M][K] (+)= dY W[:, c0:c0+K] (masked by mask > 0), / div_post
@@ -735,6 +774,8 @@ struct TG {
 
 constexpr float SQRT2 = 1.41421356237309515f;
 constexpr size_t kLgArena = (size_t)32 << 20;  // k_lgemm weight images of one call (x3)
+// rows of STLayout::lpart: 0 offset loss, 1 eikonal, 2 observed eikonal, 3 BCE, 4 d beta, 5..6 k_tr_loss ([block][2])
+constexpr size_t kLossSlots = 7;
 
 struct STLayout {
   size_t counts, mask, chunk_min, ray_off, block_sum, list, knn, tbtab, wimg, fold, inv;
@@ -742,6 +783,8 @@ struct STLayout {
   size_t raw, sdf, draw, drgb, rmin, ramin, rflag;
   size_t dYc, dHa, dHb, dC0, dZ8, ds, dG, rbar, tbar, ttbar, Ab, Zb, AX4, Ain, dWe, bsum, acc, acc3, dbeta, zero;
   size_t oblock, ptbo, Gro, Grt, ro, og, dog, tdot, Gbar, Yd, gro, wslab, lgimg;
+  size_t dpart, cpart, lpart;  // deterministic mode
+  size_t lcap;
   long N;
   size_t total;
 };
@@ -770,6 +813,12 @@ STLayout stlayout(int R, int chunk) {
   L.Grt = c.floats(N * 64); L.ro = c.floats(N * 3); L.og = c.floats(N * 4); L.dog = c.floats(N * 4);
   L.tdot = c.floats(N * 4); L.Gbar = c.floats(N * 64); L.Yd = c.floats(N * 4); L.gro = c.floats(N * 3);
   L.wslab = c.floats(wgrad_slab_floats()); L.lgimg = c.bytes(kLgArena);
+  // deterministic mode (carved in both modes: the environment can switch it per call). dpart: the generic
+  // split-K products' partials, 512-sample splits of at most 257 x 256 outputs; cpart: k_st_colsum's <= 1024
+  // blocks; lpart: kLossSlots rows of lcap per-block loss / d beta partials
+  L.lcap = (N + 255) / 256 + 2;
+  L.dpart = c.floats(gemm_det_floats(257, 256, (int)((N + 511) / 512))); L.cpart = c.floats(1024 * 256);
+  L.lpart = c.floats(kLossSlots * L.lcap);
   L.total = c.o;
   return L;
 }
@@ -960,6 +1009,21 @@ int sdf_train_core(const TrainCore& C) {
   const char* wg32_env = getenv("ANR_SDF_WG32");
   g.wg32 = !(wg32_env && wg32_env[0] == '0');
   g.slab = F(L.wslab);
+  // deterministic mode (anr_train_deterministic / ANR_TRAIN_DETERMINISTIC, read once per call as the aninerf
+  // step does): every float sum of the call in a fixed order. The pack plan above does not depend on it
+  // (weight gradients hold no weight image, and the workspace layout is the same in both modes), so the
+  // mode is not part of its key.
+  const bool det = train_det() != 0;
+  g.det = det;
+  g.det_scratch = F(L.dpart);
+  g.det_floats = (L.cpart - L.dpart) / 4;  // dpart runs up to cpart, the region carved after it
+  auto lpart = [&](int row) { return det ? F(L.lpart) + (size_t)row * L.lcap : (float*)nullptr; };
+  // *dst += the nblk per-block partials of an lpart row (from `first`, `stride` apart) in block order
+  auto det_sum = [&](int row, int first, int stride, int nblk, float* dst) {
+    DetSum d{};
+    d.src[0] = lpart(row) + first; d.n[0] = nblk; d.stride[0] = stride; d.dst[0] = dst;
+    hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(256), 0, s, d);
+  };
   const dim3 pb(256), pg((n + 255) / 256 + 1);
   auto WN = [&](int l) { return (const float*)wimg + wn_layer(l).off; };
   float* dWe = F(L.dWe);
@@ -1082,8 +1146,10 @@ int sdf_train_core(const TrainCore& C) {
       ANR_TRY(g.wgrad(m, dWN(8), 256, 0, 257, Z8, 264, Hs(7), 256, 256, grads[24]));
       ANR_TRY(g.xgrad(m, Ab, 256, 256, Z8, 264, 257, WN(8), 256, 0));
     }
-    hipLaunchKernelGGL(k_st_colsum, dim3(std::min(1024, m)), dim3(256), 0, s, (const float*)(Hs(7) + (size_t)m * 256),
-                       256L, m, dWN(8));
+    const int ncs = std::min(1024, m);
+    hipLaunchKernelGGL(k_st_colsum, dim3(ncs), dim3(256), 0, s, (const float*)(Hs(7) + (size_t)m * 256), 256L, m,
+                       dWN(8), det ? F(L.cpart) : (float*)nullptr);
+    if (det) hipLaunchKernelGGL(k_st_colsum_det, dim3(1), dim3(256), 0, s, (const float*)F(L.cpart), ncs, dWN(8));
     ANR_TRY(check_launch("k_st_colsum"));
     const float* Aprim = Z8 ? Ab : nullptr;
     const float* Atan = WN(8);  // row 0 of W8, broadcast
@@ -1210,7 +1276,13 @@ int sdf_train_core(const TrainCore& C) {
     tb.raw = raw; tb.draw = (float4*)F(L.draw); tb.n_rays = R; tb.rgb_map = out->rgb_map; tb.d_rgb_map = F(L.drgb);
     tb.n_kept = counts;
     const int gx = (R + 255) / 256;
+    tb.loss_part = lpart(5);  // deterministic mode: [block][2] partials instead of the atomic sums (2 gx <= 2 lcap)
     hipLaunchKernelGGL(k_tr_loss, dim3(gx, 1), dim3(256), 0, s, tb, C.rgb_gt, C.mask_at_box, acc3);
+    if (det) {  // squared error and mask rays, in block order into the zeroed acc3
+      det_sum(5, 0, 2, gx, acc3);
+      det_sum(5, 1, 2, gx, acc3 + 1);
+    }
+    tb.loss_part = nullptr;
     hipLaunchKernelGGL(k_tr_loss_grads, dim3(gx, 1), dim3(256), 0, s, tb, C.rgb_gt, C.mask_at_box, (const float*)acc3,
                        F(L.drgb), nullptr, nullptr);
     hipLaunchKernelGGL(k_tr_composite_bwd, dim3((R + 3) / 4), dim3(256), 0, s, tb);
@@ -1235,13 +1307,15 @@ int sdf_train_core(const TrainCore& C) {
     StRaw sr{};
     sr.list = ca.list; sr.n_kept = counts; sr.chunk = C.chunk; sr.draw = draw;
     sr.C0 = F(L.C0); sr.tbtab = tbtab; sr.Y8 = F(L.Y8); sr.Yc = F(L.Yc); sr.beta = tp[SDF_BETA];
-    sr.dYc = F(L.dYc); sr.ds = F(L.ds); sr.dbeta = F(L.dbeta);
+    sr.dYc = F(L.dYc); sr.ds = F(L.ds); sr.dbeta = F(L.dbeta); sr.dbeta_part = lpart(4);
     hipLaunchKernelGGL(k_st_raw_bwd, pg, pb, 0, s, sr);
-    if (step)
-      hipLaunchKernelGGL(k_st_msk_loss, dim3((R + 255) / 256), pb, 0, s, (const float*)F(L.rmin),
-                         (const int*)(ws + L.ramin), (const uint8_t*)(ws + L.rflag), (const int*)inv, R, alpha, F(L.ds),
-                         acc);
-    else if (C.d_sdf)
+    if (det) det_sum(4, 0, 1, (int)pg.x, F(L.dbeta));
+    if (step) {
+      const int gm = (R + 255) / 256;
+      hipLaunchKernelGGL(k_st_msk_loss, dim3(gm), pb, 0, s, (const float*)F(L.rmin), (const int*)(ws + L.ramin),
+                         (const uint8_t*)(ws + L.rflag), (const int*)inv, R, alpha, F(L.ds), acc, lpart(3));
+      if (det) det_sum(3, 0, 1, gm, acc + 3);
+    } else if (C.d_sdf)
       hipLaunchKernelGGL(k_st_cotan_sdf, pg, pb, 0, s, (const int*)ca.list, (const int*)counts, C.d_sdf, F(L.ds));
     ANR_TRY(check_launch("sdf train: raw / msk backward"));
     // ---- colour net backward (weight-normed lin4..lin0; color_latent folded into lin3)
@@ -1285,7 +1359,12 @@ int sdf_train_core(const TrainCore& C) {
       StLoss sl{};
       sl.n_kept = counts; sl.resd = F(L.resd); sl.C0 = F(L.C0); sl.dC0 = F(L.dC0); sl.ds = F(L.ds);
       sl.rbar = F(L.rbar); sl.dG = F(L.dG); sl.dZ8 = F(L.dZ8); sl.acc = acc;
+      sl.part = lpart(0); sl.part_ld = (int)L.lcap;
       hipLaunchKernelGGL(k_st_sample_loss, pg, pb, 0, s, sl);
+      if (det) {
+        det_sum(0, 0, 1, (int)pg.x, acc + 0);
+        det_sum(1, 0, 1, (int)pg.x, acc + 1);
+      }
     } else {
       hipLaunchKernelGGL(k_st_cotan_rows, pg, pb, 0, s, (const int*)counts, C.d_resd, C.d_grad, (const float*)F(L.dC0),
                          (const float*)F(L.ds), F(L.rbar), F(L.dG), F(L.dZ8));
@@ -1374,10 +1453,12 @@ int sdf_train_core(const TrainCore& C) {
     hipLaunchKernelGGL(k_st_embed_bwd10, og_, pb, 0, s, (const float*)F(L.ptbo), 8L, (const float*)Gbar, 64L, n_o, og, 4L);
     hipLaunchKernelGGL(k_st_add3, og_, pb, 0, s, (const float*)F(L.tdot), 4L, (const float*)og, 4L, n_o, og);
     if (net_fwd) return ANR_OK;  // og (n_o, 4) is an output of the call; the backward re-runs this
-    if (step)
-      hipLaunchKernelGGL(k_st_obs_loss, og_, pb, 0, s, (const float*)og, n_o, F(L.dog), acc);
-    else
+    if (step) {
+      hipLaunchKernelGGL(k_st_obs_loss, og_, pb, 0, s, (const float*)og, n_o, F(L.dog), acc, lpart(2));
+      if (det) det_sum(2, 0, 1, (int)og_.x, acc + 2);
+    } else {
       hipLaunchKernelGGL(k_st_rows3to4, og_, pb, 0, s, C.d_og, n_o, F(L.dog));
+    }
     ANR_TRY(check_launch("sdf train: observed-gradient loss"));
     // tangent forward along dog: gamma_10 -> ReLU net (masks of the primal) -> tanh -> tdot -> SDF
     float* Grt = F(L.Grt);

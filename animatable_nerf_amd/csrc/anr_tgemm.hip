@@ -1225,7 +1225,7 @@ bool wgrad_f32_fits(const WGrad& g) {
 
 static int wgrad_reduce_blocks(const WGrad& g);
 
-int launch_wgrad_f32(WGrad g, int n_host, hipStream_t s) {
+int launch_wgrad_f32(WGrad g, int n_host, hipStream_t s, bool det) {
   if (n_host <= 0) return 0;
   if (!wgrad_f32_fits(g)) return -1;
   const int ti = (g.nout + WG_T - 1) / WG_T, tj = (g.K + WG_T - 1) / WG_T;
@@ -1248,7 +1248,10 @@ int launch_wgrad_f32(WGrad g, int n_host, hipStream_t s) {
     if (dev >= 0 && dev < 64) attr[dev] = true;
   }
   hipLaunchKernelGGL(k_wgrad_f32, dim3(g.tiles * g.nz), dim3(512), WF_NB * WF_SLOT, s, g);
-  hipLaunchKernelGGL(k_wgrad_reduce, dim3(wgrad_reduce_blocks(g)), dim3(256), 0, s, g);
+  // det: every range's slab was written (a range past the samples stores its zero accumulators and zero
+  // column sums), and the fixed-order reducer honours j0 as the atomic one does
+  if (det) launch_wgrad_reduce_det(&g, 1, s);
+  else hipLaunchKernelGGL(k_wgrad_reduce, dim3(wgrad_reduce_blocks(g)), dim3(256), 0, s, g);
   return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

@@ -71,6 +71,9 @@ struct GemmArgs {
 };
 
 void launch_gemm(GemmArgs g, dim3 grid, hipStream_t s);
+// the deterministic training mode in force for this call (anr_train_capi.hip): ANR_TRAIN_DETERMINISTIC=1|0
+// when set, else anr_train_deterministic's value. Every training entry point reads it once per call.
+int train_det();
 // deterministic split-K weight gradient (the generic kernel's fixed-order route): the launch of g (atomic,
 // ksplit splits of kper, M rows) with its partials in scratch, then k_gemm_det_reduce: one thread per
 // element of C (and of rowsum) adds the live splits in ascending order, then one plain add into C /
@@ -156,9 +159,10 @@ size_t wgrad_slab_floats();
 int launch_wgrad(WGrad g, int n_host, hipStream_t s, bool det = false);
 // exact-fp32 weight gradient (k_wgrad_f32 + k_wgrad_reduce; fp32 rows, nout / K <= 256, 16-B addressable
 // rows): the exact executors' dW += dY^T X (+ bsum / bsum2 column sums), ACCUMULATED like the atomic
-// split-K GEMM it replaces; -1 (nothing launched) for a product it does not take
+// split-K GEMM it replaces; -1 (nothing launched) for a product it does not take. det: the fixed-order
+// reduction (k_wgrad_reduce_det) instead of k_wgrad_reduce's atomics
 bool wgrad_f32_fits(const WGrad& g);
-int launch_wgrad_f32(WGrad g, int n_host, hipStream_t s);
+int launch_wgrad_f32(WGrad g, int n_host, hipStream_t s, bool det = false);
 // several weight gradients in two launches (k_wgrad_group + k_wgrad_reduce_group): d[0..nd) as for
 // launch_wgrad (dY, X, dW, bsum, M_dev, formats; slab fields ignored) with nz sample ranges each, their
 // partial slabs packed into slab[0, slab_floats); more descriptors than fit one launch (WG_GROUP_MAX, or

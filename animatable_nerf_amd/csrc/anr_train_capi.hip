@@ -42,11 +42,15 @@ const size_t kLaneFloats = 4 * wgrad_slab_floats();
 //  - the latent-row updates of a flush are one launch per post, in post order;
 //  - the loss kernels store per-block partials that k_det_sum adds in block order.
 std::atomic<int> g_train_det{0};
-int train_det() {
+}  // namespace
+namespace anr {
+int train_det() {  // anr_train.h: the sdf_pdf step (anr_sdf_train.hip) reads it too
   const char* v = getenv("ANR_TRAIN_DETERMINISTIC");
   if (v && (v[0] == '0' || v[0] == '1') && v[1] == 0) return v[0] == '1';
   return g_train_det.load(std::memory_order_relaxed);
 }
+}  // namespace anr
+namespace {
 // scratch of the deterministic split-K products: 512-sample splits of at most 256 x 256 outputs
 size_t det_scratch_floats(long N) { return gemm_det_floats(256, 256, (int)((N + 511) / 512)); }
 // per-block loss partials (k_tr_loss: 2 sums x 2 rows of blocks; k_an_loss: 1)

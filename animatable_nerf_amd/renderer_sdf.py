@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from . import config as _config
+from .renderer import _cfg_deterministic
 
 CHUNK = 2048
 RAY_KEYS = ('ray_o', 'ray_d', 'near', 'far')
@@ -318,9 +319,11 @@ class _SdfTrainNetwork(torch.autograd.Function):
         sdf = torch.empty((1, n, 1), device=dev)
         tb_out = torch.empty((2, 3), device=dev)
         st = _lib.stream_ptr(dev)
-        _lib.check(lib.anr_sdf_network_train_fwd(ctypes.byref(p), ctypes.byref(c['frame']), ctypes.byref(x),
-                                                 ctypes.byref(c['opts']), _lib.ptr(raw), _lib.ptr(sdf), _lib.ptr(tb_out),
-                                                 _lib.ptr(ws), ws_bytes, st), 'anr_sdf_network_train_fwd')
+        with _lib.deterministic(_cfg_deterministic(renderer.cfg)):
+            rc = lib.anr_sdf_network_train_fwd(ctypes.byref(p), ctypes.byref(c['frame']), ctypes.byref(x),
+                                               ctypes.byref(c['opts']), _lib.ptr(raw), _lib.ptr(sdf), _lib.ptr(tb_out),
+                                               _lib.ptr(ws), ws_bytes, st)
+        _lib.check(rc, 'anr_sdf_network_train_fwd')
         addr = lib.anr_sdf_network_train_counts(_lib.ptr(ws), n)
         cnt = ws[addr - ws.data_ptr():addr - ws.data_ptr() + 16].view(torch.int32).cpu()  # host sync
         n_kept, n_obs = int(cnt[0]), int(cnt[2])
@@ -344,8 +347,11 @@ class _SdfTrainNetwork(torch.autograd.Function):
         grads = [torch.zeros_like(t) for t in params]
         gp = (ctypes.c_void_p * _lib.NUM_SDF_TENSORS)(*[g.data_ptr() for g in grads])
         keep = [t.contiguous() if t is not None else None for t in (d_raw, d_sdf, d_resd, d_grad, d_og)]
-        _lib.check(r.lib.anr_sdf_network_train_bwd(ctypes.byref(p), gp, ctypes.byref(c['frame']),
-                                                   ctypes.byref(ctx.samples[2]), ctypes.byref(c['opts']),
-                                                   *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws), ctx.ws_bytes,
-                                                   _lib.stream_ptr(dev)), 'anr_sdf_network_train_bwd')
+        # cfg.train_deterministic: the library's deterministic training mode around the call (False: left alone)
+        with _lib.deterministic(_cfg_deterministic(r.cfg)):
+            rc = r.lib.anr_sdf_network_train_bwd(ctypes.byref(p), gp, ctypes.byref(c['frame']),
+                                                 ctypes.byref(ctx.samples[2]), ctypes.byref(c['opts']),
+                                                 *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws), ctx.ws_bytes,
+                                                 _lib.stream_ptr(dev))
+        _lib.check(rc, 'anr_sdf_network_train_bwd')
         return (None, None, None, *grads)

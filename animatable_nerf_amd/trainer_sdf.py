@@ -14,6 +14,9 @@ forward-over-reverse (anr_sdf_train.hip). One call returns the losses AND every 
 * ``SdfStep(net)`` — the native loop: the 63 tensors (1,432,510 floats) and their gradients in flat
   HBM blobs with the loss floats (LOSS_KEYS) in the gradient blob's tail, so one RCCL mean all-reduce carries
   gradients and losses (DDP semantics, trainer.py:13-18); then clip + Adam (``anr_adam``).
+
+cfg ``train_deterministic`` (``SdfStep(deterministic=...)``) runs either in the library's deterministic
+training mode: every gradient and loss sum in a fixed order.
 """
 import ctypes
 
@@ -22,6 +25,7 @@ import torch
 from . import _lib
 from . import config as _config
 from .parallel import GradBuckets, broadcast_, is_dist
+from .renderer import _cfg_deterministic
 from .renderer_sdf import Renderer
 
 COLOUR_TENSORS = (28, 44)  # color_network.* (colour latent, lin0..lin4 g / v / bias): final first
@@ -83,7 +87,9 @@ class _SdfLoss(torch.autograd.Function):
     def forward(ctx, renderer, batch, t_rand, *params):
         grads = [torch.zeros_like(t) for t in params]
         loss8 = torch.zeros(NLOSS, device=params[0].device)
-        renderer.last_ret = sdf_train_step(renderer, batch, grads, loss8, t_rand)
+        # cfg.train_deterministic: the library's deterministic training mode around the step (False: left alone)
+        with _lib.deterministic(_cfg_deterministic(renderer.cfg)):
+            renderer.last_ret = sdf_train_step(renderer, batch, grads, loss8, t_rand)
         ctx.grads = grads
         return tuple(loss8[k] for k in range(6)) + (loss8[6:].detach().clone(),)
 
@@ -120,10 +126,19 @@ class SdfStep:
     The all-reduce runs in buckets as DDP's reducer does (trainer.py:13-18): bucket 0, the colour
     net's gradients, leaves on the side stream as soon as the library records them final (after the
     colour backward, ~1/5 of the blob) while the SDF / residual / observed-gradient backward still
-    runs; the rest (SDF net, beta, residual net, losses) follows the step."""
+    runs; the rest (SDF net, beta, residual net, losses) follows the step.
 
-    def __init__(self, net, cfg=None, lr=None, clip=40.0, betas=(0.9, 0.999), eps=1e-8, group=None):
+    ``deterministic=True`` (``None``: the cfg key ``train_deterministic``) runs the step in the library's
+    deterministic training mode (``anr_train_deterministic``): every gradient and loss sum in a fixed
+    order, so the same weights, batch, ``t_rand`` and ``iter_step`` give the same bits on every run. The
+    mode is set around each step's library call and restored after it (``self.deterministic`` may be
+    flipped between steps); ``ANR_TRAIN_DETERMINISTIC`` still wins inside the library. With N > 1 ranks
+    nothing more is claimed than for ``FusedStep``: the step is as deterministic as the all-reduce."""
+
+    def __init__(self, net, cfg=None, lr=None, clip=40.0, betas=(0.9, 0.999), eps=1e-8, group=None,
+                 deterministic=None):
         self.cfg = cfg if cfg is not None else _config.active()
+        self.deterministic = bool(self.cfg.get('train_deterministic', False) if deterministic is None else deterministic)
         self.net = net
         self.renderer = Renderer(net, self.cfg)
         self.lib = self.renderer.lib
@@ -180,8 +195,12 @@ class SdfStep:
         self.grad.zero_()
         it = int(batch.get('iter_step', self.iter_step))
         self._issued = False
-        sdf_train_step(self.renderer, batch, self.grad_views, self.loss8, t_rand, iter_step=it,
-                       hooks=self._hooks if is_dist() else None)
+        prev = self.lib.anr_train_deterministic(1 if self.deterministic else 0)
+        try:
+            sdf_train_step(self.renderer, batch, self.grad_views, self.loss8, t_rand, iter_step=it,
+                           hooks=self._hooks if is_dist() else None)
+        finally:
+            self.lib.anr_train_deterministic(prev)
         if not self._issued:  # CPU blob / one rank / the hook not reached (no kept sample)
             self.buckets.reduce(0)
         self.buckets.reduce(1)

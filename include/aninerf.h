@@ -348,12 +348,17 @@ int anr_train_step_hooked(const anr_params* p, float* const* grads, const anr_fr
  * produce gradients, loss3 and (through anr_adam) weights that are a function of the parameters, the batch,
  * t_rand, the precision, the shapes and the gradient buffers' contents on entry only: bit-identical from
  * run to run and whatever streams the executor uses (ANR_TRAIN_SERIAL, ANR_TRAIN_ON_CALLER, ANR_TRAIN_GRAPH).
+ * The sdf_pdf trainer honours the mode in the same way: anr_sdf_train_step(_hooked) and
+ * anr_sdf_network_train_bwd read it once per call, and their 63 gradients and the loss vector (both
+ * precisions, ANR_FP32 and ANR_BF16X3) then depend on those inputs and iter_step only. They run on the
+ * caller's stream alone; ANR_SDF_WG32=0 and ANR_SDF_LG32=0 select other kernels with another summation
+ * tree, each reproducible against itself.
  * Every weight-gradient product and its reduction then run on one stream in issue order and every float
  * sum has a fixed order (no floating-point atomics); switches that change the summation tree itself
  * (ANR_WG_GROUP, ANR_WG_DMA, ANR_WG_GROUP_NZ, ANR_WG_FILL, ANR_WG_FLUSH_EVERY, the chain switches) give
  * another, equally reproducible, result. With the mode off nothing changes.
- * Not covered: sdf_pdf training (anr_sdf_train*), which ignores the mode; and under a ray split
- * (anr_train_hooks.reduce) the result is deterministic only if the caller's all-reduce is. */
+ * Not covered: under a ray split (anr_train_hooks.reduce), and with several ranks all-reducing the sdf_pdf
+ * gradient blob, the result is deterministic only if the caller's all-reduce is. */
 int anr_train_deterministic(int on);
 int anr_adam(float* param, float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
              float beta2, float eps, float weight_decay, int step, float clip_value, void* stream);
@@ -471,7 +476,11 @@ int anr_sdf_network_rows(const void* workspace, int n_pts, float* resd, float* g
  *    d sdf (n), d resd (n',3), d gradients (n',3), d observed_gradients (n_o,3) (any NULL = 0), with the
  *    second-order terms the reference's create_graph=True input gradients carry. It re-runs the forward
  *    on the same workspace first, so f->tbounds must hold the bounds the forward call was given (before
- *    its widening). */
+ *    its widening). With the deterministic training mode on (anr_train_deterministic) every sum of the
+ *    backward has a fixed order.
+ *  anr_sdf_network_train_workspace_bytes: the same size in both training modes; it includes the
+ *    deterministic mode's scratch (per-split and per-block partials), since ANR_TRAIN_DETERMINISTIC can
+ *    switch the mode at any call. It makes no HIP call. */
 size_t anr_sdf_network_train_workspace_bytes(int n_pts);
 int anr_sdf_network_train_fwd(const anr_sdf_params* p, const anr_sdf_frame* f, const anr_samples* x,
                               const anr_render_opts* o, float* raw, float* sdf, float* tbounds_out, void* workspace,
@@ -528,7 +537,12 @@ int anr_sample_volume(const float* vol, int X, int Y, int Z, int C, const float*
  *   offset_loss, grad_loss, ograd_loss, mask_loss, img_loss, observed rows, msk_sdf entries, kept
  *   samples, 0}.
  *   out: rgb_map / acc_map / depth_map (R), tbounds_out (widened) or NULL; raw / sdf unused.
- *   Perturbation through o->t_rand; o->norm_th = 0.1. Two host reads (kept and observed counts). */
+ *   Perturbation through o->t_rand; o->norm_th = 0.1. Two host reads (kept and observed counts).
+ *   With the deterministic training mode on (anr_train_deterministic) the gradients and the loss vector
+ *   are bit-identical from run to run.
+ * anr_sdf_train_workspace_bytes: the same size in both training modes; it includes the deterministic
+ *   mode's scratch (about 1 % of the total), since ANR_TRAIN_DETERMINISTIC can switch the mode at any
+ *   call. It makes no HIP call. */
 size_t anr_sdf_train_workspace_bytes(int n_rays, const anr_render_opts* o);
 int anr_sdf_train_step(const anr_sdf_params* p, float* const* grads, const anr_sdf_frame* f, const float* ray_o,
                        const float* ray_d, const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
