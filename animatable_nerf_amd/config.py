@@ -75,6 +75,9 @@ def defaults():
         'sdf_train_precision': 'fp32',
         # deterministic training mode (anr_train_deterministic): fixed-order gradient and loss sums
         'train_deterministic': False,
+        # image-only render (anr_render_image_fwd): the render without the T-pose blend-weight MLP and the
+        # pbw / tbw rows, for evaluate / novel-view / visualise runs that want images and no training rows
+        'render_image_only': False,
         'chunk': 2048, 'mesh_th': 50.0, 'voxel_size': [0.005, 0.005, 0.005],
         'train': {'lr': 5e-4, 'weight_decay': 0.0, 'optim': 'adam', 'epoch': 400,
                   'scheduler': {'type': 'exponential', 'gamma': 0.1, 'decay_epochs': 1000}},

@@ -47,6 +47,7 @@ int num_cus() {
 }
 
 bool mlp_attr_set = false;
+bool mlp_img_attr_set = false;
 
 // measurement: event pairs around the fused network launches (anr_profile_enable / anr_profile_read),
 // and each launch's per-workgroup clock stamps (MlpArgs::clk) in a device arena of kProfSlots slots
@@ -101,19 +102,29 @@ int RaySplit::run(void* buf, int count, int op, hipStream_t s) const {
 
 int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
                    const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x, const RaySplit* split) {
+                   hipStream_t s, const anr_samples* x, const RaySplit* split, bool image) {
   const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
+  const long nt = image ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
   const int nch = (R + o->chunk - 1) / o->chunk;
   int* counts = (int*)(ws + L.counts);
 
   PrepArgs pa{};
-  pa.counts = counts;  // counts, chunk_min and chunk_max reset by k_prep's block 0
-  pa.chunk_min = (uint64_t*)(ws + L.chunk_min);
-  pa.chunk_max = (uint64_t*)(ws + L.chunk_max);
-  pa.nch = nch;
-  pa.pbw = f->pbw; pa.tbw = f->tbw;
-  pa.pbw32 = (float*)(ws + L.pbw32); pa.tbw32 = (float*)(ws + L.tbw32);
+  if (image) {
+    // an image workspace has no chunk_max for k_prep's block 0 to reset: counts (entry 1 stays 0) and
+    // chunk_min by memset, as anr_alpha_points does, and k_prep converts no T-pose volume (nt = 0)
+    if (hipMemsetAsync(counts, 0, 16, s) != hipSuccess ||
+        hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess)
+      return fail(ANR_E_HIP, "hipMemsetAsync failed");
+    pa.pbw = f->pbw;
+    pa.pbw32 = (float*)(ws + L.pbw32);
+  } else {
+    pa.counts = counts;  // counts, chunk_min and chunk_max reset by k_prep's block 0
+    pa.chunk_min = (uint64_t*)(ws + L.chunk_min);
+    pa.chunk_max = (uint64_t*)(ws + L.chunk_max);
+    pa.nch = nch;
+    pa.pbw = f->pbw; pa.tbw = f->tbw;
+    pa.pbw32 = (float*)(ws + L.pbw32); pa.tbw32 = (float*)(ws + L.tbw32);
+  }
   pa.np = (int)np; pa.nt = (int)nt;
   pa.w_bw0 = p->t[28]; pa.b_bw0 = p->t[29]; pa.w_bw5 = p->t[38]; pa.b_bw5 = p->t[39];
   pa.bw_latent = p->t[27]; pa.w_lat = p->t[21]; pa.b_lat = p->t[22]; pa.nf_latent = p->t[0];
@@ -189,7 +200,7 @@ int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, 
 // the fused network kernel (render path)
 int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
               const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x) {
+              hipStream_t s, const anr_samples* x, bool image) {
   const long N = (long)R * 64;
   MlpArgs ma{};
   if (x) {
@@ -201,15 +212,20 @@ int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const
   ma.fold = (const float*)(ws + L.fold);
   ma.A = f->A; ma.R = f->R; ma.Th = f->Th;
   ma.pbw32 = (const float*)(ws + L.pbw32); ma.pbounds = f->pbounds;
-  ma.tbw32 = (const float*)(ws + L.tbw32); ma.tbounds = f->tbounds;
+  ma.tbounds = f->tbounds;
   ma.pX = f->pbw_dims[0]; ma.pY = f->pbw_dims[1]; ma.pZ = f->pbw_dims[2];
-  ma.tX = f->tbw_dims[0]; ma.tY = f->tbw_dims[1]; ma.tZ = f->tbw_dims[2];
+  if (!image) {
+    ma.tbw32 = (const float*)(ws + L.tbw32);
+    ma.tX = f->tbw_dims[0]; ma.tY = f->tbw_dims[1]; ma.tZ = f->tbw_dims[2];
+  }
   ma.ray_o = ray_o; ma.ray_d = ray_d; ma.near_ = near_; ma.far_ = far_; ma.t_rand = o->t_rand;
   ma.list = (const int*)(ws + L.list); ma.n_kept = (const int*)(ws + L.counts);
   ma.raw = raw;
-  ma.sigma = (float*)(ws + L.sigma);
-  ma.pbw_rows = (float*)(ws + L.pbw_rows);
-  ma.tbw_rows = (float*)(ws + L.tbw_rows);
+  if (!image) {  // the image program writes raw alone
+    ma.sigma = (float*)(ws + L.sigma);
+    ma.pbw_rows = (float*)(ws + L.pbw_rows);
+    ma.tbw_rows = (float*)(ws + L.tbw_rows);
+  }
   const bool x6 = o->precision == ANR_BF16X6;
   const bool b16 = o->precision == ANR_BF16X3 || x6;
   ma.pose_woff = o->novel_pose ? (x6 || (b16 && ANR_POSE_MODE == 2) ? ANR_X6_NOVEL_WOFF : b16 ? ANR_B16_NOVEL_WOFF : ANR_NOVEL_WOFF) : 0;
@@ -225,10 +241,27 @@ int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const
       return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp) failed");
     mlp_attr_set = true;
   }
+  if (image && !mlp_img_attr_set) {
+    if (hipFuncSetAttribute((const void*)k_mlp_img, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            mlp_lds_bytes<false>()) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_mlp_img_b16, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            mlp_lds_bytes<true>()) != hipSuccess ||
+        hipFuncSetAttribute((const void*)k_mlp_img_x6, hipFuncAttributeMaxDynamicSharedMemorySize,
+                            mlp_lds_bytes<true>()) != hipSuccess)
+      return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_img) failed");
+    mlp_img_attr_set = true;
+  }
   const long max_tiles = (N + 127) / 128;
   const int grid = (int)(max_tiles < num_cus() ? max_tiles : num_cus());
   ProfSlot* ps = prof_begin(s, grid);
   ma.clk = ps ? ps->clk : nullptr;
+  if (image) {
+    if (x6) hipLaunchKernelGGL(k_mlp_img_x6, dim3(grid), dim3(512), lds, s, ma);
+    else if (b16) hipLaunchKernelGGL(k_mlp_img_b16, dim3(grid), dim3(512), lds, s, ma);
+    else hipLaunchKernelGGL(k_mlp_img, dim3(grid), dim3(512), lds, s, ma);
+    ANR_TRY(check_launch("k_mlp_img"));
+    return prof_end(ps, s);
+  }
   if (x6) hipLaunchKernelGGL(k_mlp_x6, dim3(grid), dim3(512), lds, s, ma);
   else if (b16) hipLaunchKernelGGL(k_mlp_b16, dim3(grid), dim3(512), lds, s, ma);
   else hipLaunchKernelGGL(k_mlp, dim3(grid), dim3(512), lds, s, ma);
@@ -501,6 +534,48 @@ int anr_render_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, 
   ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s));
   ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s));
   ANR_TRY(stage_alpha_ind(n_rays, o, ws, L, s));
+  return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s);
+}
+
+// ---- image-only render (include/aninerf.h): front-end -> image program -> compositing ------
+size_t anr_render_image_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f) {
+  if (!o || !f || n_rays <= 0 || o->chunk <= 0) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (f->pbw_dims[i] <= 0) return 0;
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  return layout_image(n_rays, o->chunk, np, true).total;
+}
+
+int anr_render_image_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                         const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                         const anr_render_out* out, void* workspace, size_t ws_bytes, void* stream) {
+  if (!p || !f || !o || !out || !workspace) return fail(ANR_E_ARG, "anr_render_image_fwd: NULL argument");
+  if (o->n_samples != 64) return fail(ANR_E_ARG, "anr_render_image_fwd: only N_samples == 64 is supported");
+  if (o->chunk <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: chunk must be > 0");
+  if (n_rays <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: n_rays must be > 0");
+  if ((long)n_rays * 64 > 0x7fffffffL / 24) return fail(ANR_E_ARG, "anr_render_image_fwd: too many rays for one call");
+  if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
+    return fail(ANR_E_ARG, "anr_render_image_fwd: NULL tensor");
+  for (int i = 0; i < 3; ++i)
+    if (f->pbw_dims[i] <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: bad volume dims");
+  if (!f->A || !f->R || !f->Th || !f->pbw || !f->pbounds || !f->tbounds || !f->latent_index)
+    return fail(ANR_E_ARG, "anr_render_image_fwd: NULL frame tensor");
+  if (o->novel_pose) {
+    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
+      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_render_image_fwd: novel_pose needs the novel_pose_bw tensors");
+    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_render_image_fwd: novel_pose needs bw_latent_index");
+  }
+  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
+    return fail(ANR_E_ARG, "anr_render_image_fwd: bad visibility-filter views");
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  const Layout L = layout_image(n_rays, o->chunk, np, out->raw == nullptr);
+  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_render_image_fwd: workspace too small");
+
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float4* raw = out->raw ? (float4*)out->raw : (float4*)(ws + L.raw);
+  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, nullptr, true));
+  ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, true));
   return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s);
 }
 

@@ -240,6 +240,10 @@ __global__ void k_prep(PrepArgs a);
 __global__ void k_mlp(MlpArgs a);
 __global__ void k_mlp_b16(MlpArgs a);  // T-pose BW + NeRF in bf16x3 (render precision ANR_BF16X3)
 __global__ void k_mlp_x6(MlpArgs a);   // every layer in bf16x6, fp32-level (render precision ANR_BF16X6)
+// image render program (anr_mlp_body.h V = 9 / 19): k_mlp* without the T-pose BW pass, rows and sigma
+__global__ void k_mlp_img(MlpArgs a);
+__global__ void k_mlp_img_b16(MlpArgs a);
+__global__ void k_mlp_img_x6(MlpArgs a);
 __global__ void k_alpha(MlpArgs a);      // density program (get_alpha), exact fp32 MFMA
 __global__ void k_alpha_b16(MlpArgs a);  // density program, NeRF trunk in bf16x3
 __global__ void k_alpha_x6(MlpArgs a);   // density program, every layer in bf16x6

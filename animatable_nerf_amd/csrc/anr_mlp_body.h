@@ -89,12 +89,16 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 //   V = 13, 15, 16, 17 (render precision ANR_BF16X6 of the sdf_pdf render): the programs 3, 5, 6, 7
 //         with every entry in mode 2 (bf16x6, fp32-level products), from bf16x6 sequence images
 //         (k_pack_seq_x6), the softplus and its backward factor at libm accuracy.
+//   V = 9 (image render, k_mlp_img exact fp32 and k_mlp_img_b16 bf16x3): the V = 2 program without the
+//         T-pose BW pass, whose only product is the tbw rows of the training loss: entries 0..8 the
+//         pose-space BW MLP, 9..16 the NeRF trunk (layers 9..16), 17 the folded colour head
+//         (ANR_L_HEAD), 18 rgb_fc. V = 19 (k_mlp_img_x6): the same program with every entry in mode 2.
 template <int V>
 __host__ __device__ constexpr int prog_base() { return V >= 10 ? V - 10 : V; }
 template <int V>
 __host__ __device__ constexpr int prog_len() {
   constexpr int B = prog_base<V>();
-  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5) ? 9 : B == 7 ? 8 : B == 6 ? 5 : 18;  // 1, 8: 18
+  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5) ? 9 : B == 7 ? 8 : B == 6 ? 5 : B == 9 ? 19 : 18;  // 1, 8: 18
 }
 // programs whose weights are a packed layer sequence of their own (k_pack_seq), not the render image
 template <int V>
@@ -111,6 +115,7 @@ __host__ __device__ constexpr int prog_layer(int e) {
          : e < 9 ? e
          : V == 0 ? e - 9
          : (V == 2 || V == 4) ? (e < 26 ? e - 9 : (e == 26 ? ANR_L_HEAD : ANR_L_RGB))
+         : V == 9 ? (e < 17 ? e : (e == 17 ? ANR_L_HEAD : ANR_L_RGB))
          : V == 8 ? (e < 17 ? e : ANR_L_ALPHA)
                   : (e < 17 ? e : ANR_L_ALPHA);
 }
@@ -404,6 +409,29 @@ static_assert(prog_bias_off<1>(prog_len<1>()) <= ANR_BIAS_TABLE_FLOATS, "bias ta
 static_assert(prog_bias_off<2>(prog_len<2>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
 static_assert(prog_bias_off<4>(prog_len<4>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
 static_assert(prog_bias_off<8>(prog_len<8>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
+static_assert(prog_bias_off<9>(prog_len<9>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
+static_assert(prog_bias_off<19>(prog_len<19>()) == prog_bias_off<9>(prog_len<9>()), "image render: one bias table");
+
+// exact fp32 MFMAs a wave issues per tile over entries [e0, e1) of program V: k-steps x out-blocks
+template <int V>
+__host__ __device__ constexpr int prog_f32_mfmas(int e0, int e1) {
+  int n = 0;
+  for (int e = e0; e < e1; ++e) n += layer_ksteps(prog_layer<V>(e)) * layer_desc_all(prog_layer<V>(e)).ob;
+  return n;
+}
+// the image render program is the render program minus its T-pose BW pass (entries 9..17), layer for
+// layer and in the same order, so that every surviving layer sees the operands it sees there
+static_assert(prog_f32_mfmas<9>(0, prog_len<9>()) == prog_f32_mfmas<2>(0, prog_len<2>()) - prog_f32_mfmas<2>(9, 18),
+              "image render program: the render program without entries 9..17");
+static_assert(prog_f32_mfmas<9>(0, prog_len<9>()) == 16168, "image render program: fp32 MFMAs per tile and wave");
+constexpr bool img_prog_matches() {
+  for (int e = 0; e < 9; ++e)
+    if (prog_layer<9>(e) != prog_layer<2>(e) || prog_layer<19>(e) != prog_layer<4>(e)) return false;
+  for (int e = 9; e < 19; ++e)
+    if (prog_layer<9>(e) != prog_layer<2>(e + 9) || prog_layer<19>(e) != prog_layer<4>(e + 9)) return false;
+  return true;
+}
+static_assert(img_prog_matches(), "image render program: layers of the render program, T-pose pass removed");
 static_assert(prog_bias_off<3>(prog_len<3>()) == seq_bias_off(ANR_L_RESD0, ANR_RESD_LAYERS), "resd bias section");
 static_assert(prog_bias_off<5>(prog_len<5>()) == seq_bias_off(ANR_L_SDF0, ANR_SDF_LAYERS), "sdf bias section");
 static_assert(prog_bias_off<5>(prog_len<5>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
@@ -432,7 +460,7 @@ __device__ __forceinline__ void fill_bias_table(const MlpArgs& a, float* __restr
       src = e == 3 ? a.fold + 512 : a.bias + toff;
     } else if constexpr (e < 9) {
       src = L == 0 ? a.fold + 0 : L == 5 ? a.fold + 512 : a.bias + a.pose_boff + boff;
-    } else if constexpr (V != 1 && V != 8 && e < 18) {
+    } else if constexpr (VB != 1 && VB != 8 && VB != 9 && e < 18) {
       src = L == 0 ? a.fold + 256 : L == 5 ? a.fold + 768 : a.bias + boff;
     } else {
       src = L == 18 ? a.fold + 1024 : L == ANR_L_HEAD ? a.fold + ANR_FOLD_HEAD : a.bias + boff;
@@ -1250,12 +1278,31 @@ __device__ __forceinline__ void bw_mlp(Pipe& p, const float (&emb)[16], const fl
   layer<B16, V, E0 + 8, false, true>(p, B, emb, vemb, fc, sb, g, lane);
 }
 
-template <bool B16, int V = 2>
+// IMG (the image render programs V = 9 / 19, k_mlp_img*): the tile without its T-pose BW pass. raw, and
+// with it rgb_map / acc_map / depth_map, is a function of xt, which the pose pass and the LBS inverse
+// produce; the T-pose pass only fills the tbw rows of the training loss. No tbw lookup, no second BW
+// MLP, no row stores, no sigma (the alpha_ind stage that reads it is not run on an image workspace).
+// hides a lane index from loop-invariant code motion (embed() below)
+__device__ __forceinline__ int launder_lane(int x) {
+  asm volatile("" : "+v"(x));
+  return x;
+}
+template <bool B16, int V = 2, bool IMG = false>
 __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
   // every kernel runs the folded colour head (anr_layers.h ANR_L_HEAD): 131,072 fewer MACs per sample
-  static_assert(V == 2 || V == 4, "render programs");
+  static_assert(IMG ? (V == 9 || V == 19) : (V == 2 || V == 4), "render programs");
   // hardware log/exp/rcp and reciprocal lookup coordinates only in the bf16x3 kernel
-  constexpr bool FAST = B16 && ANR_FAST_MATH && V == 2;
+  constexpr bool FAST = B16 && ANR_FAST_MATH && (V == 2 || V == 9);
+  constexpr int N0 = IMG ? 9 : 18;  // the NeRF's first program entry
+  // The exact fp32 image kernel (k_mlp_img) alone, for its register budget: without the T-pose pass between
+  // them the pose pass and the NeRF meet in one allocation problem, and what k_mlp carries across its layers
+  // no longer fits 256 VGPRs. Same operations on the same operands, only when they are issued: embed()'s
+  // per-lane feature indices formed at each call (as embed_b() does) instead of hoisted out of the tile loop,
+  // the pbw lookup after the BW MLP instead of before it (init is not live across the nine layers), the bbox
+  // test right after the LBS inverse (one flag instead of xt across the NeRF), dist and the view direction
+  // read again before the colour head instead of carried from the top of the tile, and no free-sample branch
+  // (anr_render_image_fwd takes rays).
+  constexpr bool F32I = IMG && !B16;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1282,7 +1329,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
     const bool valid = idx < n;
     const int pid = a.list[valid ? idx : n - 1];
     float dist, pose[3], dir[3];
-    if (a.dists) {  // free samples (Network.forward): the caller's world point, view direction, dist
+    if (!F32I && a.dists) {  // free samples (Network.forward): the caller's world point, view direction, dist
       world_to_pose_pt(a.wpts, pid, a.n_pts, a.chunk_pts, a.R, a.Th, pose);
       dist = a.dists[pid];
 #pragma unroll
@@ -1301,52 +1348,76 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
 
     // ---- pose space: pbw lookup, BW MLP (latent_index + 1), softmax, LBS
     if constexpr (B16) embed_b<2>(pose, g, 10, emb);
+    else if constexpr (F32I) embed<16>(pose, launder_lane(g), 10, emb);
     else embed<16>(pose, g, 10, emb);
-    lookup24<FAST>(a.pbw32, pose, a.pbounds, a.pX, a.pY, a.pZ, g, init);
+    if constexpr (!F32I) lookup24<FAST>(a.pbw32, pose, a.pbounds, a.pX, a.pY, a.pZ, g, init);
 #pragma unroll
     for (int s8 = 0; s8 < 8; ++s8) vemb[s8] = 0.f;
     bw_mlp<B16, V, 0>(p, emb, vemb, sb, A, B, fc, g, lane);
+    if constexpr (F32I) lookup24<FAST>(a.pbw32, pose, a.pbounds, a.pX, a.pY, a.pZ, g, init);
     blend_softmax<FAST>(fc, init, g, bw);
-    store_rows(a.pbw_rows, idx, bw, g, valid);
+    if constexpr (!IMG) store_rows(a.pbw_rows, idx, bw, g, valid);
     float xt[3];
     lbs_inverse(bw, sA, g, pose, xt);
+    bool inside_early = true;
+    if constexpr (F32I) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) inside_early = inside_early && (xt[c] > sT[c]) && (xt[c] < sT[3 + c]);
+    }
 
     // ---- T-pose: tbw lookup, BW MLP (latent 0) -> tbw rows (training loss only)
     if constexpr (B16) embed_b<2>(xt, g, 10, emb);
+    else if constexpr (F32I) embed<16>(xt, launder_lane(g), 10, emb);
     else embed<16>(xt, g, 10, emb);
-    lookup24<FAST>(a.tbw32, xt, a.tbounds, a.tX, a.tY, a.tZ, g, init);
-    bw_mlp<B16, V, 9>(p, emb, vemb, sb, A, B, fc, g, lane);
-    blend_softmax<FAST>(fc, init, g, bw);
-    store_rows(a.tbw_rows, idx, bw, g, valid);
+    if constexpr (!IMG) {
+      lookup24<FAST>(a.tbw32, xt, a.tbounds, a.tX, a.tY, a.tZ, g, init);
+      bw_mlp<B16, V, 9>(p, emb, vemb, sb, A, B, fc, g, lane);
+      blend_softmax<FAST>(fc, init, g, bw);
+      store_rows(a.tbw_rows, idx, bw, g, valid);
+    }
 
     // ---- canonical NeRF (TPoseHuman.calculate_alpha_rgb)
     f32x4 dummy[1];
-    layer<B16, V, 18, true>(p, dummy, emb, vemb, A, sb, g, lane);
-    layer<B16, V, 19, true, true>(p, A, emb, vemb, B, sb, g, lane);
-    layer<B16, V, 20, true, true>(p, B, emb, vemb, A, sb, g, lane);
-    layer<B16, V, 21, true, true>(p, A, emb, vemb, B, sb, g, lane);
-    layer<B16, V, 22, true, true>(p, B, emb, vemb, A, sb, g, lane);
-    layer<B16, V, 23, true, true>(p, A, emb, vemb, B, sb, g, lane);
-    layer<B16, V, 24, true, true>(p, B, emb, vemb, A, sb, g, lane);
-    layer<B16, V, 25, true, true>(p, A, emb, vemb, B, sb, g, lane);
+    layer<B16, V, N0 + 0, true>(p, dummy, emb, vemb, A, sb, g, lane);
+    layer<B16, V, N0 + 1, true, true>(p, A, emb, vemb, B, sb, g, lane);
+    layer<B16, V, N0 + 2, true, true>(p, B, emb, vemb, A, sb, g, lane);
+    layer<B16, V, N0 + 3, true, true>(p, A, emb, vemb, B, sb, g, lane);
+    layer<B16, V, N0 + 4, true, true>(p, B, emb, vemb, A, sb, g, lane);
+    layer<B16, V, N0 + 5, true, true>(p, A, emb, vemb, B, sb, g, lane);
+    layer<B16, V, N0 + 6, true, true>(p, B, emb, vemb, A, sb, g, lane);
+    layer<B16, V, N0 + 7, true, true>(p, A, emb, vemb, B, sb, g, lane);
     float sigma_raw;
+    if constexpr (F32I) {
+      int pid2 = pid;
+      asm volatile("" : "+v"(pid2));
+      const int ray = pid2 >> 6, s = pid2 & 63;
+      float z, pts[3];
+      sample_point(a.ray_o, a.ray_d, a.near_, a.far_, a.t_rand, ray, s, 64, z, dist, pts);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dir[c] = a.ray_d[3 * ray + c];
+    }
     if constexpr (B16) embed_b<1>(dir, g, 4, vemb);
+    else if constexpr (F32I) embed<8>(dir, launder_lane(g), 4, vemb);
     else embed<8>(dir, g, 4, vemb);
-    layer<B16, V, 26, false, true>(p, B, emb, vemb, A, sb, g, lane);  // view_fc pre-activation || alpha
+    layer<B16, V, N0 + 8, false, true>(p, B, emb, vemb, A, sb, g, lane);  // view_fc pre-activation || alpha
     sigma_raw = __shfl(A[8][0], pl);
-    if constexpr (!(prog_mode<B16, V>(27) == 1 && x3_stream_layer<ANR_L_RGB>())) {  // else rgb_fc applies view_fc's ReLU in its split
+    if constexpr (!(prog_mode<B16, V>(N0 + 9) == 1 && x3_stream_layer<ANR_L_RGB>())) {  // else rgb_fc applies view_fc's ReLU in its split
       static_for<0, 8>([&](auto ob) {
         constexpr int o = decltype(ob)::value;
 #pragma unroll
         for (int r = 0; r < 4; ++r) A[o][r] = fmaxf(A[o][r], 0.0f);
       });
     }
-    layer<B16, V, 27, false, true>(p, A, emb, vemb, B, sb, g, lane);  // rgb_fc
+    layer<B16, V, N0 + 9, false, true>(p, A, emb, vemb, B, sb, g, lane);  // rgb_fc
 
     // ---- bbox mask, activations, outputs
     bool inside = true;
+    if constexpr (F32I) {
+      inside = inside_early;
+    } else {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) inside = inside && (xt[c] > sT[c]) && (xt[c] < sT[3 + c]);
+      for (int c = 0; c < 3; ++c) inside = inside && (xt[c] > sT[c]) && (xt[c] < sT[3 + c]);
+    }
     const float sig = inside ? sigma_raw : 0.0f;
     if (valid && g == 0) {
       float4 r;
@@ -1355,7 +1426,7 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
       r.z = 1.0f / (1.0f + expf(-B[0][2]));
       r.w = 1.0f - expf(-fmaxf(sig, 0.0f) * dist);
       a.raw[pid] = r;
-      a.sigma[idx] = sig;
+      if constexpr (!IMG) a.sigma[idx] = sig;
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the last (unused) prefetch

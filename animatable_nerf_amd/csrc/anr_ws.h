@@ -57,6 +57,27 @@ inline Layout layout(int n_rays, int chunk, long np, long nt, bool need_raw) {
   return L;
 }
 
+// Image-only render (anr_render_image_fwd): what the front-end, the image program and the compositing
+// touch. No sigma, flags, block_sum2, out_row, pbw_rows, tbw_rows, chunk_max, tbw32: those fields stay 0
+// and nothing of an image render may read them. counts is at offset 0 as in layout() (anr_render_counts).
+inline Layout layout_image(int n_rays, int chunk, long np, bool need_raw) {
+  Layout L{};
+  const size_t R = (size_t)n_rays, N = R * 64;
+  Carve c;
+  L.counts = c.bytes(16);
+  L.mask = c.bytes(R * 8);
+  L.ray_off = c.bytes((R + 1) * 4);
+  L.block_sum = c.bytes(((R + 255) / 256) * 4);
+  L.list = c.bytes(N * 4);
+  const size_t nch = (R + chunk - 1) / (chunk > 0 ? chunk : 1);
+  L.chunk_min = c.bytes(nch * 8);
+  L.raw = need_raw ? c.bytes(N * 16) : 0;
+  L.pbw32 = c.bytes((size_t)np * 32 * 4);
+  L.pn24 = c.bytes((size_t)np * 4);
+  L.fold = c.bytes(ANR_FOLD_FLOATS * 4);
+  L.total = c.o;
+  return L;
+}
 
 int fail(int code, const std::string& msg);
 int check_launch(const char* what);
@@ -74,14 +95,15 @@ struct RaySplit {
   int run(void* buf, int count, int op, hipStream_t s) const;
 };
 
+// image: the image-only render on a layout_image() workspace (no T-pose volume, rows or alpha_ind state)
 // x != NULL: free samples (Network.forward): R = ceil(n_pts / 64) groups of 64 samples, the caller's
 // opts with chunk = R (the whole call is one reference chunk) and no t_rand; ray pointers unused
 int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
                    const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x = nullptr, const RaySplit* split = nullptr);
+                   hipStream_t s, const anr_samples* x = nullptr, const RaySplit* split = nullptr, bool image = false);
 int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
               const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x = nullptr);
+              hipStream_t s, const anr_samples* x = nullptr, bool image = false);
 int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, hipStream_t s,
                     const RaySplit* split = nullptr);
 int stage_composite(const float* near_, const float* far_, int R, const anr_render_opts* o, const float4* raw,

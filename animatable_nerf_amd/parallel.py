@@ -202,7 +202,12 @@ def render_sharded(renderer, batch, chunk=2048, group=None, rows=False):
     is chunk order. The large row outputs (aninerf 'pbw' / 'tbw' alpha_ind rows, sdf_pdf 'resd' /
     'gradients' kept rows: ~1.1 GB per 512x512 frame, padded to the largest rank's count by the
     all-gather) are gathered only when rows=True; otherwise each rank keeps its own shard's rows
-    under 'pbw_local' etc. 'span' = this rank's rays [start, end)."""
+    under 'pbw_local' etc. 'span' = this rank's rays [start, end).
+    Under the cfg key render_image_only (the aninerf renderers) every shard is an image-only render:
+    the image keys alone are gathered, there are no rows, and rows=True raises ValueError."""
+    image_only = bool(getattr(renderer, '_image_only', lambda: False)())
+    if image_only and rows:
+        raise ValueError('render_sharded: rows=True under render_image_only: an image-only render has no rows')
     rank = dist.get_rank(group) if is_dist() else 0
     world = dist.get_world_size(group) if is_dist() else 1
     R = int(batch['ray_o'].shape[1])
@@ -221,7 +226,7 @@ def render_sharded(renderer, batch, chunk=2048, group=None, rows=False):
             out.update(sdf=torch.zeros((1, 0, 1), device=dev), resd=torch.zeros((1, 0, 3), device=dev),
                        gradients=torch.zeros((1, 0, 3), device=dev), msk_sdf=torch.zeros((1, 0), device=dev),
                        msk_label=torch.zeros((1, 0), device=dev))
-        else:
+        elif not image_only:
             out.update(pbw=torch.zeros((1, 0, 24), device=dev), tbw=torch.zeros((1, 0, 24), device=dev))
     if widens:  # every rank leaves the frame's bounds as the whole single-GPU render does
         from .renderer_sdf import widen_tbounds

@@ -183,6 +183,9 @@ class Renderer:
         """The workspace of the last render_device() call. render() renders a frame in parts on two
         workspaces, so after it no single workspace describes the frame: use last_counts there."""
         ws = getattr(self, '_last_ws', None)
+        if ws is None and getattr(self, '_last_image_only', False):
+            raise RuntimeError(f'Renderer.{what}: the last render was image-only (render_image_only): its workspace '
+                               'holds no alpha_ind rows and its counts were not read')
         if ws is None:
             raise RuntimeError(f'Renderer.{what} describes the last render_device() call; the last render was '
                                'render() (the frame in parts): use Renderer.last_counts')
@@ -205,21 +208,49 @@ class Renderer:
         return t_rand
 
     # ---- render -----------------------------------------------------------------------------
-    def render_device(self, batch, t_rand=None, bw_rows=True):
+    def _image_only(self, image_only=None):
+        """The image-only switch of a call: the argument, or (None) the cfg key render_image_only."""
+        return bool(self.cfg.get('render_image_only', False)) if image_only is None else bool(image_only)
+
+    def _render_fwd(self, c, p, R, attr, image_only):
+        """anr_render_fwd (image_only: anr_render_image_fwd) of call `c` into workspace `attr` of the entry's
+        own size, on the current stream; no host read. -> the workspace."""
+        dev = c.dev
+        size_fn, fwd, name = ((self.lib.anr_render_image_workspace_bytes, self.lib.anr_render_image_fwd,
+                               'anr_render_image_fwd') if image_only else
+                              (self.lib.anr_render_workspace_bytes, self.lib.anr_render_fwd, 'anr_render_fwd'))
+        ws_bytes = size_fn(R, ctypes.byref(c.opts), ctypes.byref(c.frame))
+        ws = self._workspace(attr, ws_bytes, dev)
+        c.opts.precision = c.render_precision
+        _lib.check(fwd(ctypes.byref(p), ctypes.byref(c.frame), *c.ray_ptrs(), R, ctypes.byref(c.opts),
+                       ctypes.byref(c.out), _lib.ptr(ws), ws_bytes, _lib.stream_ptr(dev)), name)
+        return ws
+
+    def render_device(self, batch, t_rand=None, bw_rows=None, image_only=None):
         """Evaluation render on the GPU (fused network kernel); all returned tensors stay in HBM.
         ``t_rand`` (R, N_samples) overrides the stratification draws (tests); by default they are
-        drawn when perturb > 0 and the network is in training mode (tpose_renderer.py:29-36)."""
+        drawn when perturb > 0 and the network is in training mode (tpose_renderer.py:29-36).
+        ``image_only`` (None: the cfg key render_image_only): the image render program, which leaves out
+        the T-pose blend-weight MLP and the alpha_ind rows: the same rgb_map / acc_map / depth_map / raw,
+        no pbw / tbw, no count read (no host sync; last_counts stays None, row_ids() / counts() raise).
+        ``bw_rows`` (None: not image_only) adds the pbw / tbw rows, which an image-only render does not have."""
+        image_only = self._image_only(image_only)
+        if bw_rows is None:
+            bw_rows = not image_only
+        if image_only and bw_rows:
+            raise ValueError('render_device: an image-only render (render_image_only) has no pbw / tbw rows; '
+                             'pass bw_rows=False or image_only=False')
         p = self.params()
         dev = self._packed.device
         R = batch['ray_o'].shape[1]
         c = _Call(self, batch, self._t_rand(R, dev, t_rand))
-        ws_bytes = self.lib.anr_render_workspace_bytes(R, ctypes.byref(c.opts), ctypes.byref(c.frame))
-        ws = self._workspace('_ws', ws_bytes, dev)
-        c.opts.precision = c.render_precision
-        _lib.check(self.lib.anr_render_fwd(ctypes.byref(p), ctypes.byref(c.frame), *c.ray_ptrs(), R,
-                                           ctypes.byref(c.opts), ctypes.byref(c.out), _lib.ptr(ws), ws_bytes,
-                                           _lib.stream_ptr(dev)), 'anr_render_fwd')
-        self._last_ws = ws
+        ws = self._render_fwd(c, p, R, '_ws', image_only)
+        self._last_image_only = image_only
+        if image_only:
+            self._last_ws = None
+            self.last_counts = None
+        else:
+            self._last_ws = ws
         ret = {'rgb_map': c.rgb, 'acc_map': c.acc, 'depth_map': c.depth, 'raw': c.raw}
         if bw_rows:
             ret['pbw'], ret['tbw'] = self._bw_rows(ws, R, dev)
@@ -253,21 +284,59 @@ class Renderer:
         with torch.no_grad():
             if parts < 2 or not self.device().type == 'cuda':
                 return to_host(self.render_device(batch))
+            if self._image_only():
+                return self._render_overlapped_image(batch, R, chunk, parts)
             return self._render_overlapped(batch, R, chunk, parts)
 
-    def _render_launch(self, batch, attr):
-        """anr_render_fwd of one part on the current stream into workspace `attr`, no host read."""
+    def _render_launch(self, batch, attr, image_only=False):
+        """anr_render_fwd (image_only: anr_render_image_fwd) of one part on the current stream into
+        workspace `attr`, no host read."""
         p = self.params()
         dev = self._packed.device
         R = batch['ray_o'].shape[1]
         c = _Call(self, batch, self._t_rand(R, dev, None))
-        ws_bytes = self.lib.anr_render_workspace_bytes(R, ctypes.byref(c.opts), ctypes.byref(c.frame))
-        ws = self._workspace(attr, ws_bytes, dev)
-        c.opts.precision = c.render_precision
-        _lib.check(self.lib.anr_render_fwd(ctypes.byref(p), ctypes.byref(c.frame), *c.ray_ptrs(), R,
-                                           ctypes.byref(c.opts), ctypes.byref(c.out), _lib.ptr(ws), ws_bytes,
-                                           _lib.stream_ptr(dev)), 'anr_render_fwd')
+        ws = self._render_fwd(c, p, R, attr, image_only)
         return c, ws, R
+
+    def _render_overlapped_image(self, batch, R, chunk, parts):
+        """_render_overlapped under render_image_only: the same parts of whole chunks on two alternating
+        workspaces, part k's four image outputs crossing to page-locked host buffers on the side stream
+        while part k + 1 renders. No row buffers, no row extraction, no per-part count read."""
+        from .parallel import RAY_KEYS as SLICED, shard_chunks
+        dev = self.device()
+        ns = int(self.cfg.N_samples)
+        with torch.cuda.device(dev):
+            if getattr(self, '_copy_stream', None) is None:
+                self._copy_stream = torch.cuda.Stream(dev)
+            cs = self._copy_stream
+            cur = torch.cuda.current_stream(dev)
+            pin = dict(dtype=torch.float32, pin_memory=True)
+            h = {'rgb_map': torch.empty((1, R, 3), **pin), 'acc_map': torch.empty((1, R), **pin),
+                 'depth_map': torch.empty((1, R), **pin), 'raw': torch.empty((1, R * ns, 4), **pin)}
+            keep = []  # the parts' device tensors, alive until their copies are done
+            for k in range(parts):
+                a, b = shard_chunks(R, k, parts, chunk)
+                if a >= b:
+                    continue
+                sub = {key_: (v[:, a:b] if key_ in SLICED and torch.is_tensor(v) else v) for key_, v in batch.items()}
+                # a part's outputs are its own tensors and nothing is read back from its workspace, so the
+                # next part on the same workspace needs no wait beyond the stream's own order
+                c, _, _ = self._render_launch(sub, '_ws' if k % 2 == 0 else '_ws_b', image_only=True)
+                launched = torch.cuda.Event()
+                launched.record(cur)
+                with torch.cuda.stream(cs):
+                    cs.wait_event(launched)
+                    h['rgb_map'][:, a:b].copy_(c.rgb, non_blocking=True)
+                    h['acc_map'][:, a:b].copy_(c.acc, non_blocking=True)
+                    h['depth_map'][:, a:b].copy_(c.depth, non_blocking=True)
+                    h['raw'][:, a * ns:b * ns].copy_(c.raw, non_blocking=True)
+                keep.append(c)
+            cs.synchronize()
+            cur.wait_stream(cs)
+        self._last_ws = None
+        self._last_image_only = True
+        self.last_counts = None
+        return h
 
     def _render_overlapped(self, batch, R, chunk, parts):
         """The frame in parts of whole chunks (per-chunk semantics unchanged: the rows of the parts,
@@ -293,6 +362,7 @@ class Renderer:
                  'depth_map': torch.empty((1, R), **pin), 'raw': torch.empty((1, R * ns, 4), **pin)}
             st = dict(late=[], kept=0, off=0, hp=None, ht=None, keep=[], k=0)
             self._last_ws = None  # the parts alternate between two workspaces (row_ids / counts refuse)
+            self._last_image_only = False
             # the previous frame's row count, when it had the same rays (another frame size: extrapolated)
             est_R, est_m = getattr(self, '_rows_est', (0, 0))
             est = int(est_m) if est_R == R else 0

@@ -236,6 +236,24 @@ int anr_render_bw_rows(const void* workspace, int n_rays, float* pbw, float* tbw
  * which samples tpose_nerf_network.py:192-196 selected (rows compared by sample in tests). */
 int anr_render_row_ids(const void* workspace, int n_rays, int32_t* ids, void* stream);
 
+/* ---- image-only render --------------------------------------------------------------------
+ * anr_render_fwd for callers that want images and no training rows (evaluation, novel views,
+ * visualisation): the same rgb_map / acc_map / depth_map / raw, bit for bit, from the image render
+ * program, which leaves out the T-pose blend-weight MLP (tpose_nerf_network.py:170-174; it only fills
+ * the tbw rows of the loss) and the alpha_ind stage. The visibility filter (f->n_views), novel_pose,
+ * t_rand and the three render precisions work as in anr_render_fwd.
+ *  f->tbw and f->tbw_dims are not read (NULL / zeros are fine); f->tbounds is (the T-pose bbox mask).
+ *  The workspace has a smaller layout of its own (no pbw / tbw rows, no row bookkeeping, no tbw copy).
+ *    anr_render_counts works on it: entry 0 is the kept count, entry 1 is 0. anr_render_bw_rows and
+ *    anr_render_row_ids are invalid on an image workspace (there are no rows).
+ *  anr_render_image_workspace_bytes returns 0 for NULL o / f, n_rays <= 0, o->chunk <= 0 or a
+ *    non-positive pbw dim.
+ *  ANR_E_ARG / ANR_E_WORKSPACE before any HIP call, for what anr_render_fwd rejects minus tbw. */
+size_t anr_render_image_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f);
+int anr_render_image_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                         const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                         const anr_render_out* out, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- Network.forward over free samples (tpose_nerf_network.py:139-215) ----------------------
  * The call a reference renderer makes per chunk, self.net(wpts, viewdir, dists, batch)
  * (tpose_renderer.py:95): n_pts samples given by world points wpts (n,3), view directions viewdir
