@@ -9,7 +9,9 @@ SRCS := $(SRC_DIR)/anr_capi.hip $(SRC_DIR)/anr_rays.hip $(SRC_DIR)/anr_mlp.hip $
         $(SRC_DIR)/anr_sdf_train.hip $(SRC_DIR)/anr_resd_b16.hip $(SRC_DIR)/anr_resd_x6.hip $(SRC_DIR)/anr_mlp_x6.hip $(SRC_DIR)/anr_alpha_x6.hip $(SRC_DIR)/anr_tchain.hip \
         $(SRC_DIR)/anr_eval.hip $(SRC_DIR)/anr_bwvol.hip $(SRC_DIR)/anr_meshcc.hip \
         $(SRC_DIR)/anr_meshdist.hip \
-        $(SRC_DIR)/anr_mlp_img.hip $(SRC_DIR)/anr_mlp_img_b16.hip $(SRC_DIR)/anr_mlp_img_x6.hip
+        $(SRC_DIR)/anr_mlp_img.hip $(SRC_DIR)/anr_mlp_img_b16.hip $(SRC_DIR)/anr_mlp_img_x6.hip \
+        $(SRC_DIR)/anr_rays_ns.hip $(SRC_DIR)/anr_mlp_ns.hip $(SRC_DIR)/anr_mlp_b16_ns.hip $(SRC_DIR)/anr_mlp_x6_ns.hip \
+        $(SRC_DIR)/anr_mlp_img_ns.hip $(SRC_DIR)/anr_mlp_img_b16_ns.hip $(SRC_DIR)/anr_mlp_img_x6_ns.hip
 OBJS := $(SRCS:.hip=.o)
 DEPS := $(OBJS:.o=.d)
 LIB := animatable_nerf_amd/libaninerf_hip.so
@@ -36,6 +38,7 @@ $(TESTLIB): $(OBJS) $(TESTOBJ)
 # v_pk_add_f32, which costs more issue cycles beside MFMAs than two v_sub_f32 (same-box A/B round 6:
 # sdf_pdf bf16x6 frame 180.0 -> 175.8 ms, k_mlp_x6 cycles -2.4 %, profiles/round6/r8b_*)
 $(SRC_DIR)/anr_mlp_x6.o $(SRC_DIR)/anr_resd_x6.o $(SRC_DIR)/anr_mlp_img_x6.o: CXXFLAGS += -fno-slp-vectorize
+$(SRC_DIR)/anr_mlp_x6_ns.o $(SRC_DIR)/anr_mlp_img_x6_ns.o: CXXFLAGS += -fno-slp-vectorize
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@.tmp $(OBJS) && mv -f $@.tmp $@
@@ -48,6 +51,10 @@ resources: $(SRC_DIR)/anr_mlp.hip $(SRC_DIR)/anr_mlp_b16.hip
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_mlp_img.hip -o /tmp/anr_mlp_img_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_mlp_img_b16.hip -o /tmp/anr_mlp_img_b16_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -fno-slp-vectorize -c $(SRC_DIR)/anr_mlp_img_x6.hip -o /tmp/anr_mlp_img_x6_res.o -Rpass-analysis=kernel-resource-usage
+	for u in anr_mlp_ns anr_mlp_b16_ns anr_mlp_img_ns anr_mlp_img_b16_ns; do \
+	  $(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/$$u.hip -o /tmp/$${u}_res.o -Rpass-analysis=kernel-resource-usage || exit 1; done
+	for u in anr_mlp_x6_ns anr_mlp_img_x6_ns; do \
+	  $(HIPCC) $(CXXFLAGS) -fno-slp-vectorize -c $(SRC_DIR)/$$u.hip -o /tmp/$${u}_res.o -Rpass-analysis=kernel-resource-usage || exit 1; done
 
 clean:
 	rm -f $(OBJS) $(DEPS) $(LIB) $(TESTOBJ) $(TESTLIB)

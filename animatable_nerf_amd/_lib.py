@@ -39,6 +39,7 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_bw_volume', 'anr_mesh_cc_workspace_bytes', 'anr_mesh_cc_count', 'anr_mesh_cc_emit',
            'anr_mesh_dist_workspace_bytes', 'anr_mesh_sample', 'anr_mesh_point_dist', 'anr_mesh_metrics', 'anr_mesh_order',
            'anr_render_image_workspace_bytes', 'anr_render_image_fwd',
+           'anr_render_ns_workspace_bytes', 'anr_render_ns_fwd', 'anr_render_ns_bw_rows', 'anr_render_ns_row_ids',
            'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
@@ -196,6 +197,13 @@ def load():
     lib.anr_render_image_workspace_bytes.restype = ctypes.c_size_t
     lib.anr_render_image_workspace_bytes.argtypes = lib.anr_render_workspace_bytes.argtypes
     lib.anr_render_image_fwd.argtypes = lib.anr_render_fwd.argtypes
+    lib.anr_render_ns_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_render_ns_workspace_bytes.argtypes = lib.anr_render_workspace_bytes.argtypes + [ctypes.c_int]
+    lib.anr_render_ns_fwd.argtypes = [ctypes.POINTER(Params), ctypes.POINTER(Frame), P, P, P, P, ctypes.c_int,
+                                      ctypes.POINTER(RenderOpts), ctypes.POINTER(RenderOut), ctypes.c_int, P,
+                                      ctypes.c_size_t, P]
+    lib.anr_render_ns_bw_rows.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P, P]
+    lib.anr_render_ns_row_ids.argtypes = [P, ctypes.c_int, ctypes.c_int, P, P]
     lib.anr_render_counts.restype = P
     lib.anr_render_counts.argtypes = [P, ctypes.c_int]
     lib.anr_render_bw_rows.argtypes = [P, ctypes.c_int, P, P, P]

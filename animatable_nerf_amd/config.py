@@ -92,6 +92,30 @@ def defaults():
     })
 
 
+RENDER_N_SAMPLES = (64, 128, 192, 256)  # cfg.N_samples the aninerf render programs take (anr_render_ns_fwd)
+
+
+def render_n_samples(cfg, who):
+    """cfg.N_samples for the aninerf render programs: 64, 128, 192 or 256, else ValueError (before any
+    library call)."""
+    ns = int(cfg.N_samples)
+    if ns not in RENDER_N_SAMPLES:
+        raise ValueError(f'{who}: N_samples = {ns}: the render programs take {", ".join(map(str, RENDER_N_SAMPLES[:-1]))} '
+                         f'or {RENDER_N_SAMPLES[-1]} samples per ray')
+    return ns
+
+
+def require_64_samples(cfg, who):
+    """Training, the animation stage and the sdf_pdf programs run 64 samples per ray only: anything else is a
+    ValueError here, before any library call (only the aninerf render programs take 128, 192 or 256)."""
+    ns = int(cfg.N_samples)
+    if ns != 64:
+        raise ValueError(f'{who}: N_samples = {ns}: 64 only (64 samples per ray is the one count training, the '
+                         'animation stage and the sdf_pdf programs support; the aninerf render programs '
+                         '(Renderer.render / render_device without grad) also take 128, 192 or 256)')
+    return ns
+
+
 # The keys of each named experiment that reach the hot path (the yaml files are not shipped: the
 # reference tree is not available where the GPU tests run). Each overrides defaults() (= aninerf_s9p).
 SUBJECTS = {

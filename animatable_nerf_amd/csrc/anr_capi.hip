@@ -48,6 +48,7 @@ int num_cus() {
 
 bool mlp_attr_set = false;
 bool mlp_img_attr_set = false;
+bool mlp_ns_attr_set = false;
 
 // measurement: event pairs around the fused network launches (anr_profile_enable / anr_profile_read),
 // and each launch's per-workgroup clock stamps (MlpArgs::clk) in a device arena of kProfSlots slots
@@ -102,7 +103,7 @@ int RaySplit::run(void* buf, int count, int op, hipStream_t s) const {
 
 int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
                    const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x, const RaySplit* split, bool image) {
+                   hipStream_t s, const anr_samples* x, const RaySplit* split, bool image, int nseg) {
   const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
   const long nt = image ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
   const int nch = (R + o->chunk - 1) / o->chunk;
@@ -170,6 +171,9 @@ int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, 
     fa.chunk_pts = x->n_pts;
     hipLaunchKernelGGL(k_frontend_pts, dim3((R + 3) / 4), dim3(256), 0, s, fa);
     ANR_TRY(check_launch("k_frontend_pts"));
+  } else if (nseg > 0) {  // R, chunk and ray_offset in rows
+    hipLaunchKernelGGL(k_frontend_ns, dim3((R + 15) / 16), dim3(1024), 0, s, fa, nseg);
+    ANR_TRY(check_launch("k_frontend_ns"));
   } else {
     hipLaunchKernelGGL(k_frontend, dim3((R + 15) / 16), dim3(1024), 0, s, fa);
     ANR_TRY(check_launch("k_frontend"));
@@ -200,7 +204,7 @@ int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, 
 // the fused network kernel (render path)
 int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
               const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x, bool image) {
+              hipStream_t s, const anr_samples* x, bool image, int nseg) {
   const long N = (long)R * 64;
   MlpArgs ma{};
   if (x) {
@@ -251,10 +255,35 @@ int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const
       return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_img) failed");
     mlp_img_attr_set = true;
   }
+  if (nseg > 0 && !mlp_ns_attr_set) {
+    const void* k32[2] = {(const void*)k_mlp_ns, (const void*)k_mlp_img_ns};
+    const void* k16[4] = {(const void*)k_mlp_b16_ns, (const void*)k_mlp_x6_ns, (const void*)k_mlp_img_b16_ns,
+                          (const void*)k_mlp_img_x6_ns};
+    for (const void* k : k32)
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<false>()) != hipSuccess)
+        return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_ns) failed");
+    for (const void* k : k16)
+      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<true>()) != hipSuccess)
+        return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_ns) failed");
+    mlp_ns_attr_set = true;
+  }
   const long max_tiles = (N + 127) / 128;
   const int grid = (int)(max_tiles < num_cus() ? max_tiles : num_cus());
   ProfSlot* ps = prof_begin(s, grid);
   ma.clk = ps ? ps->clk : nullptr;
+  if (nseg > 0) {  // N_samples = 64 * nseg: the programs with the general id decode
+    if (image) {
+      if (x6) hipLaunchKernelGGL(k_mlp_img_x6_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+      else if (b16) hipLaunchKernelGGL(k_mlp_img_b16_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+      else hipLaunchKernelGGL(k_mlp_img_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+    } else {
+      if (x6) hipLaunchKernelGGL(k_mlp_x6_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+      else if (b16) hipLaunchKernelGGL(k_mlp_b16_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+      else hipLaunchKernelGGL(k_mlp_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
+    }
+    ANR_TRY(check_launch("k_mlp_ns"));
+    return prof_end(ps, s);
+  }
   if (image) {
     if (x6) hipLaunchKernelGGL(k_mlp_img_x6, dim3(grid), dim3(512), lds, s, ma);
     else if (b16) hipLaunchKernelGGL(k_mlp_img_b16, dim3(grid), dim3(512), lds, s, ma);
@@ -308,10 +337,14 @@ int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, 
 
 // A12 compositing
 int stage_composite(const float* near_, const float* far_, int R, const anr_render_opts* o, const float4* raw,
-                    const anr_render_out* out, float* weights, hipStream_t s) {
+                    const anr_render_out* out, float* weights, hipStream_t s, int nseg) {
   CompositeArgs co{};
   co.raw = raw; co.near_ = near_; co.far_ = far_; co.t_rand = o->t_rand; co.n_rays = R;
   co.rgb = out->rgb_map; co.acc = out->acc_map; co.depth = out->depth_map; co.weights = weights;
+  if (nseg > 0) {
+    hipLaunchKernelGGL(k_composite_ns, dim3((R + 3) / 4), dim3(256), 0, s, co, nseg);
+    return check_launch("k_composite_ns");
+  }
   hipLaunchKernelGGL(k_composite, dim3((R + 3) / 4), dim3(256), 0, s, co);
   return check_launch("k_composite");
 }
@@ -577,6 +610,94 @@ int anr_render_image_fwd(const anr_params* p, const anr_frame* f, const float* r
   ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, nullptr, true));
   ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, true));
   return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s);
+}
+
+// ---- render at N_samples = 64, 128, 192 or 256 (include/aninerf.h) --------------------------
+// A ray is nseg = N_samples / 64 rows of 64 samples: the workspace is layout() / layout_image() of
+// n_rays * nseg rows with chunk * nseg rows per chunk, so every region that scaled with R * 64 scales
+// with R * N_samples and the number of chunks is unchanged.
+static int ns_segments(int n_samples) {
+  return (n_samples == 64 || n_samples == 128 || n_samples == 192 || n_samples == 256) ? n_samples / 64 : 0;
+}
+// rows and rows per chunk as ints: 24 * n_rays * n_samples < 2^31 bounds the rows; the chunk is clamped to the
+// call's rays (a chunk no call can fill behaves like one chunk), so chunk * nseg fits too
+static bool ns_rows(int n_rays, const anr_render_opts* o, int nseg, int* rows, int* chunk_rows) {
+  if (n_rays <= 0 || o->chunk <= 0 || nseg <= 0) return false;
+  if ((long)n_rays * nseg * 64 > 0x7fffffffL / 24) return false;
+  *rows = n_rays * nseg;
+  *chunk_rows = (o->chunk < n_rays ? o->chunk : n_rays) * nseg;
+  return true;
+}
+
+size_t anr_render_ns_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f, int image_only) {
+  if (!o || !f) return 0;
+  int rows, chunk_rows;
+  if (!ns_rows(n_rays, o, ns_segments(o->n_samples), &rows, &chunk_rows)) return 0;
+  for (int i = 0; i < 3; ++i)
+    if (f->pbw_dims[i] <= 0 || (!image_only && f->tbw_dims[i] <= 0)) return 0;
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  if (image_only) return layout_image(rows, chunk_rows, np, true).total;
+  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
+  return layout(rows, chunk_rows, np, nt, true).total;
+}
+
+int anr_render_ns_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                      const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                      const anr_render_out* out, int image_only, void* workspace, size_t ws_bytes, void* stream) {
+  if (!p || !f || !o || !out || !workspace) return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL argument");
+  const int nseg = ns_segments(o->n_samples);
+  if (nseg == 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: N_samples must be 64, 128, 192 or 256");
+  if (o->chunk <= 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: chunk must be > 0");
+  if (n_rays <= 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: n_rays must be > 0");
+  int rows, chunk_rows;
+  if (!ns_rows(n_rays, o, nseg, &rows, &chunk_rows))
+    return fail(ANR_E_ARG, "anr_render_ns_fwd: too many rays for one call (24 n_rays N_samples must stay below 2^31)");
+  if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
+    return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL tensor");
+  for (int i = 0; i < 3; ++i)
+    if (f->pbw_dims[i] <= 0 || (!image_only && f->tbw_dims[i] <= 0))
+      return fail(ANR_E_ARG, "anr_render_ns_fwd: bad volume dims");
+  if (!f->A || !f->R || !f->Th || !f->pbw || (!image_only && !f->tbw) || !f->pbounds || !f->tbounds || !f->latent_index)
+    return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL frame tensor");
+  if (o->novel_pose) {
+    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
+      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_render_ns_fwd: novel_pose needs the novel_pose_bw tensors");
+    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_render_ns_fwd: novel_pose needs bw_latent_index");
+  }
+  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
+    return fail(ANR_E_ARG, "anr_render_ns_fwd: bad visibility-filter views");
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  const long nt = image_only ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
+  const bool img = image_only != 0;
+  const Layout L = img ? layout_image(rows, chunk_rows, np, out->raw == nullptr)
+                       : layout(rows, chunk_rows, np, nt, out->raw == nullptr);
+  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_render_ns_fwd: workspace too small");
+
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  float4* raw = out->raw ? (float4*)out->raw : (float4*)(ws + L.raw);
+  anr_render_opts oo = *o;
+  oo.chunk = chunk_rows;  // the stages below count in rows
+  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, rows, &oo, ws, L, raw, s, nullptr, nullptr, img, nseg));
+  ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, rows, &oo, ws, L, raw, s, nullptr, img, nseg));
+  if (!img) ANR_TRY(stage_alpha_ind(rows, &oo, ws, L, s));
+  return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s, nseg);
+}
+
+int anr_render_ns_bw_rows(const void* workspace, int n_rays, int n_samples, float* pbw, float* tbw, void* stream) {
+  const int nseg = ns_segments(n_samples);
+  if (nseg == 0) return fail(ANR_E_ARG, "anr_render_ns_bw_rows: N_samples must be 64, 128, 192 or 256");
+  if (n_rays <= 0 || (long)n_rays * n_samples > 0x7fffffffL / 24)
+    return fail(ANR_E_ARG, "anr_render_ns_bw_rows: bad n_rays");
+  return anr_render_bw_rows(workspace, n_rays * nseg, pbw, tbw, stream);
+}
+
+int anr_render_ns_row_ids(const void* workspace, int n_rays, int n_samples, int32_t* ids, void* stream) {
+  const int nseg = ns_segments(n_samples);
+  if (nseg == 0) return fail(ANR_E_ARG, "anr_render_ns_row_ids: N_samples must be 64, 128, 192 or 256");
+  if (n_rays <= 0 || (long)n_rays * n_samples > 0x7fffffffL / 24)
+    return fail(ANR_E_ARG, "anr_render_ns_row_ids: bad n_rays");
+  return anr_render_row_ids(workspace, n_rays * nseg, ids, stream);
 }
 
 // ---- Network.forward over free samples (include/aninerf.h) --------------------------------

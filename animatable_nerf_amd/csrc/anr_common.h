@@ -19,6 +19,13 @@ __device__ __forceinline__ float linspace01(int i, int n) {
   return (i < half) ? fmaf(step, (float)i, 0.0f) : fmaf(-step, (float)(n - 1 - i), 1.0f);
 }
 
+// N_samples = 64 * nseg (nseg = 1..4): a ray is nseg rows of 64 samples, row = ray * nseg + seg, so a
+// sample id is row * 64 + lane == ray * N_samples + s. floor(row / nseg): a shift for 1, 2, 4; for 3
+// the multiply-high by ceil(2^32 / 3), exact for row < 2^31.
+__device__ __forceinline__ int ns_ray_of_row(int row, int nseg) {
+  return nseg == 3 ? (int)__umulhi((unsigned)row, 0x55555556u) : row >> (nseg >> 1);
+}
+
 // One trilinear lookup in the layout of blend_utils.py:119-149 / ATen grid_sampler_3d (CPU):
 // volume memory (X,Y,Z,C) viewed as (C, D=X, H=Y, W=Z); grid = normalised (z, y, x).
 struct TriCell {

@@ -244,6 +244,18 @@ __global__ void k_mlp_x6(MlpArgs a);   // every layer in bf16x6, fp32-level (ren
 __global__ void k_mlp_img(MlpArgs a);
 __global__ void k_mlp_img_b16(MlpArgs a);
 __global__ void k_mlp_img_x6(MlpArgs a);
+// N_samples = 64 * nseg, nseg = 1..4 (anr_render_ns_fwd): a ray is nseg rows of 64 samples. The front-end and
+// the compositing of anr_rays_ns.hip (FrontArgs::n_rays / chunk / ray_offset in rows; CompositeArgs::n_rays in
+// rays) and the six render programs with the general id decode (anr_mlp_body.h NS); every other kernel of the
+// render path runs over rows as it stands
+__global__ void k_frontend_ns(FrontArgs a, int nseg);
+__global__ void k_composite_ns(CompositeArgs a, int nseg);
+__global__ void k_mlp_ns(MlpArgs a, int nseg);
+__global__ void k_mlp_b16_ns(MlpArgs a, int nseg);
+__global__ void k_mlp_x6_ns(MlpArgs a, int nseg);
+__global__ void k_mlp_img_ns(MlpArgs a, int nseg);
+__global__ void k_mlp_img_b16_ns(MlpArgs a, int nseg);
+__global__ void k_mlp_img_x6_ns(MlpArgs a, int nseg);
 __global__ void k_alpha(MlpArgs a);      // density program (get_alpha), exact fp32 MFMA
 __global__ void k_alpha_b16(MlpArgs a);  // density program, NeRF trunk in bf16x3
 __global__ void k_alpha_x6(MlpArgs a);   // density program, every layer in bf16x6

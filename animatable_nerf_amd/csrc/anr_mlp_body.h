@@ -1287,8 +1287,10 @@ __device__ __forceinline__ int launder_lane(int x) {
   asm volatile("" : "+v"(x));
   return x;
 }
-template <bool B16, int V = 2, bool IMG = false>
-__device__ __forceinline__ void mlp_body(const MlpArgs& a) {
+// NS (the k_mlp*_ns kernels of anr_render_ns_fwd): N_samples = 64 * nseg, a kept id is row * 64 + lane with
+// row = ray * nseg + seg (anr_common.h ns_ray_of_row); without it nseg is unused and a ray is one row.
+template <bool B16, int V = 2, bool IMG = false, bool NS = false>
+__device__ __forceinline__ void mlp_body(const MlpArgs& a, int nseg = 1) {
   // every kernel runs the folded colour head (anr_layers.h ANR_L_HEAD): 131,072 fewer MACs per sample
   static_assert(IMG ? (V == 9 || V == 19) : (V == 2 || V == 4), "render programs");
   // hardware log/exp/rcp and reciprocal lookup coordinates only in the bf16x3 kernel
@@ -1335,9 +1337,14 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) dir[c] = a.vdir[3 * (size_t)pid + c];
     } else {
-      const int ray = pid >> 6, s = pid & 63;
+      // F32I: nseg made opaque per tile, so what sample_point derives from N_samples (1 / (n - 1) and the like, VALU
+      // results in VGPRs) is formed here and not hoisted out of the tile loop into kernel-lifetime registers
+      int k = nseg;
+      if constexpr (NS && F32I) asm volatile("" : "+s"(k));
+      const int ray = NS ? ns_ray_of_row(pid >> 6, k) : pid >> 6;
+      const int ns = NS ? k * 64 : 64, s = NS ? pid - ray * ns : pid & 63;
       float z, pts[3];
-      sample_point(a.ray_o, a.ray_d, a.near_, a.far_, a.t_rand, ray, s, 64, z, dist, pts);
+      sample_point(a.ray_o, a.ray_d, a.near_, a.far_, a.t_rand, ray, s, ns, z, dist, pts);
       world_to_pose(pts, a.R, a.Th, pose);
 #pragma unroll
       for (int c = 0; c < 3; ++c) dir[c] = a.ray_d[3 * ray + c];
@@ -1390,9 +1397,12 @@ __device__ __forceinline__ void mlp_body(const MlpArgs& a) {
     if constexpr (F32I) {
       int pid2 = pid;
       asm volatile("" : "+v"(pid2));
-      const int ray = pid2 >> 6, s = pid2 & 63;
+      int k = nseg;
+      if constexpr (NS) asm volatile("" : "+s"(k));  // as at the tile top
+      const int ray = NS ? ns_ray_of_row(pid2 >> 6, k) : pid2 >> 6;
+      const int ns = NS ? k * 64 : 64, s = NS ? pid2 - ray * ns : pid2 & 63;
       float z, pts[3];
-      sample_point(a.ray_o, a.ray_d, a.near_, a.far_, a.t_rand, ray, s, 64, z, dist, pts);
+      sample_point(a.ray_o, a.ray_d, a.near_, a.far_, a.t_rand, ray, s, ns, z, dist, pts);
 #pragma unroll
       for (int c = 0; c < 3; ++c) dir[c] = a.ray_d[3 * ray + c];
     }

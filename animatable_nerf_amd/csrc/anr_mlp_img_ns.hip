@@ -1,0 +1,9 @@
+// anr_mlp_img_ns.hip — k_mlp_img_ns: the image render program k_mlp_img (exact fp32 MFMA; anr_mlp_body.h V = 9) at
+// N_samples = 64 * nseg (anr_render_ns_fwd): the same layers, the kept ids decoded as row * 64 + lane.
+#include "anr_mlp_body.h"
+
+namespace anr {
+
+__global__ __launch_bounds__(512) void k_mlp_img_ns(MlpArgs a, int nseg) { ANR_STAMPED(mlp_body<false, 9, true, true>(a, nseg);); }
+
+}  // namespace anr

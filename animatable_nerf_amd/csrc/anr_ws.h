@@ -98,15 +98,20 @@ struct RaySplit {
 // image: the image-only render on a layout_image() workspace (no T-pose volume, rows or alpha_ind state)
 // x != NULL: free samples (Network.forward): R = ceil(n_pts / 64) groups of 64 samples, the caller's
 // opts with chunk = R (the whole call is one reference chunk) and no t_rand; ray pointers unused
+// nseg > 0 (anr_render_ns_fwd): N_samples = 64 * nseg. R, o->chunk and the layout are then in rows (a ray is
+// nseg rows of 64 samples: R = n_rays * nseg, chunk = rays per chunk * nseg) for stage_frontend, stage_mlp and
+// stage_alpha_ind, whose compaction and alpha_ind kernels run over rows as over rays; stage_composite takes rays.
+// nseg == 0: the 64-sample kernels.
 int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
                    const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x = nullptr, const RaySplit* split = nullptr, bool image = false);
+                   hipStream_t s, const anr_samples* x = nullptr, const RaySplit* split = nullptr, bool image = false,
+                   int nseg = 0);
 int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
               const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x = nullptr, bool image = false);
+              hipStream_t s, const anr_samples* x = nullptr, bool image = false, int nseg = 0);
 int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, hipStream_t s,
                     const RaySplit* split = nullptr);
 int stage_composite(const float* near_, const float* far_, int R, const anr_render_opts* o, const float4* raw,
-                    const anr_render_out* out, float* weights, hipStream_t s);
+                    const anr_render_out* out, float* weights, hipStream_t s, int nseg = 0);
 
 }  // namespace anr

@@ -4,7 +4,8 @@ One call renders every ray of the batch through the C-ABI: sampling, prefilter, 
 canonical NeRF and compositing run as device kernels, with the reference's 2048-ray chunk semantics
 (forced argmin keep, forced argmax loss row) preserved without a chunk loop on the host. Output keys
 and shapes are the reference's: ``rgb_map (1,R,3)``, ``acc_map (1,R)``, ``depth_map (1,R)``,
-``raw (1,R*64,4)``, ``pbw/tbw (1,m,24)``.
+``raw (1,R*N_samples,4)``, ``pbw/tbw (1,m,24)``. ``cfg.N_samples`` is 64, or for the no-grad render 128, 192
+or 256 (``anr_render_ns_fwd``; training takes 64 only).
 
 * no grad (evaluation, run.py:63-69): the fused single-kernel network (``anr_render_fwd``); outputs
   are moved to the CPU by ``render`` as the reference does (tpose_renderer.py:154-155),
@@ -170,13 +171,22 @@ class Renderer:
         self.last_counts = (int(c[0]), int(c[1]))
         return self.last_counts
 
-    def _bw_rows(self, ws, R, dev):
+    def _gather_rows(self, ws, R, pbw, tbw, dev, ns=64):
+        """the alpha_ind rows of a workspace of R rays at ns samples into pbw / tbw (64: anr_render_bw_rows,
+        else the entry of the other sample counts)"""
+        if ns == 64:
+            _lib.check(self.lib.anr_render_bw_rows(_lib.ptr(ws), R, _lib.ptr(pbw), _lib.ptr(tbw), _lib.stream_ptr(dev)),
+                       'anr_render_bw_rows')
+        else:
+            _lib.check(self.lib.anr_render_ns_bw_rows(_lib.ptr(ws), R, ns, _lib.ptr(pbw), _lib.ptr(tbw),
+                                                      _lib.stream_ptr(dev)), 'anr_render_ns_bw_rows')
+
+    def _bw_rows(self, ws, R, dev, ns=64):
         _, m = self._counts(ws, R)
         pbw = torch.empty((1, m, 24), device=dev)
         tbw = torch.empty((1, m, 24), device=dev)
         if m > 0:
-            _lib.check(self.lib.anr_render_bw_rows(_lib.ptr(ws), R, _lib.ptr(pbw), _lib.ptr(tbw), _lib.stream_ptr(dev)),
-                       'anr_render_bw_rows')
+            self._gather_rows(ws, R, pbw, tbw, dev, ns)
         return pbw, tbw
 
     def _last_device_ws(self, what):
@@ -195,11 +205,15 @@ class Renderer:
         """Sample ids (ray * N_samples + sample) of the alpha_ind rows of the last render_device(), (m,)
         int64 on the device, in row order (anr_render_row_ids)."""
         ws = self._last_device_ws('row_ids()')
+        ns = getattr(self, '_last_ns', 64)  # the sample count the workspace was rendered at
         _, m = self._counts(ws, n_rays)
         ids = torch.empty((m,), dtype=torch.int32, device=ws.device)
-        if m > 0:
+        if m > 0 and ns == 64:
             _lib.check(self.lib.anr_render_row_ids(_lib.ptr(ws), n_rays, _lib.ptr(ids),
                                                    _lib.stream_ptr(ws.device)), 'anr_render_row_ids')
+        elif m > 0:
+            _lib.check(self.lib.anr_render_ns_row_ids(_lib.ptr(ws), n_rays, ns, _lib.ptr(ids),
+                                                      _lib.stream_ptr(ws.device)), 'anr_render_ns_row_ids')
         return ids.long()
 
     def _t_rand(self, R, dev, t_rand):
@@ -214,8 +228,19 @@ class Renderer:
 
     def _render_fwd(self, c, p, R, attr, image_only):
         """anr_render_fwd (image_only: anr_render_image_fwd) of call `c` into workspace `attr` of the entry's
-        own size, on the current stream; no host read. -> the workspace."""
+        own size, on the current stream; no host read. -> the workspace. N_samples 128, 192 or 256: the same
+        two programs through anr_render_ns_fwd (64 keeps the entries above)."""
         dev = c.dev
+        ns = int(c.opts.n_samples)
+        if ns != 64:
+            io = 1 if image_only else 0
+            ws_bytes = self.lib.anr_render_ns_workspace_bytes(R, ctypes.byref(c.opts), ctypes.byref(c.frame), io)
+            ws = self._workspace(attr, ws_bytes, dev)
+            c.opts.precision = c.render_precision
+            _lib.check(self.lib.anr_render_ns_fwd(ctypes.byref(p), ctypes.byref(c.frame), *c.ray_ptrs(), R,
+                                                  ctypes.byref(c.opts), ctypes.byref(c.out), io, _lib.ptr(ws), ws_bytes,
+                                                  _lib.stream_ptr(dev)), 'anr_render_ns_fwd')
+            return ws
         size_fn, fwd, name = ((self.lib.anr_render_image_workspace_bytes, self.lib.anr_render_image_fwd,
                                'anr_render_image_fwd') if image_only else
                               (self.lib.anr_render_workspace_bytes, self.lib.anr_render_fwd, 'anr_render_fwd'))
@@ -240,12 +265,14 @@ class Renderer:
         if image_only and bw_rows:
             raise ValueError('render_device: an image-only render (render_image_only) has no pbw / tbw rows; '
                              'pass bw_rows=False or image_only=False')
+        ns = _config.render_n_samples(self.cfg, 'Renderer.render_device')
         p = self.params()
         dev = self._packed.device
         R = batch['ray_o'].shape[1]
         c = _Call(self, batch, self._t_rand(R, dev, t_rand))
         ws = self._render_fwd(c, p, R, '_ws', image_only)
         self._last_image_only = image_only
+        self._last_ns = ns
         if image_only:
             self._last_ws = None
             self.last_counts = None
@@ -253,12 +280,13 @@ class Renderer:
             self._last_ws = ws
         ret = {'rgb_map': c.rgb, 'acc_map': c.acc, 'depth_map': c.depth, 'raw': c.raw}
         if bw_rows:
-            ret['pbw'], ret['tbw'] = self._bw_rows(ws, R, dev)
+            ret['pbw'], ret['tbw'] = self._bw_rows(ws, R, dev, ns)
         return ret
 
     def render_train(self, batch, t_rand=None):
         """Training forward (autograd-enabled): returns the render dict; ``rgb_map``, ``pbw`` and
         ``tbw`` carry gradients to every network parameter through ``anr_train_bwd``."""
+        _config.require_64_samples(self.cfg, 'Renderer.render_train')
         dev = self.device()
         R = batch['ray_o'].shape[1]
         t_rand = self._t_rand(R, dev, t_rand)
@@ -276,6 +304,7 @@ class Renderer:
     def render(self, batch):
         if torch.is_grad_enabled() and any(p.requires_grad for p in self.net.parameters()) and self.net.training:
             return self.render_train(batch)
+        _config.render_n_samples(self.cfg, 'Renderer.render')
         R = batch['ray_o'].shape[1]
         chunk = int(self.cfg.get('chunk', CHUNK))
         n_chunks = (R + chunk - 1) // chunk
@@ -378,8 +407,7 @@ class Renderer:
                     pr = torch.empty((1, n, 24), device=dev)
                     tr = torch.empty((1, n, 24), device=dev)
                     if n:
-                        _lib.check(self.lib.anr_render_bw_rows(_lib.ptr(ws), Rp, _lib.ptr(pr), _lib.ptr(tr),
-                                                               _lib.stream_ptr(dev)), 'anr_render_bw_rows')
+                        self._gather_rows(ws, Rp, pr, tr, dev, ns)
                     ev = torch.cuda.Event()
                     ev.record(cs)
                     ws_free[slot] = ev

@@ -87,6 +87,7 @@ class Renderer:
     def prepare(self, batch, t_rand=None, chunk_offset=0):
         """Device tensors and C structs of one call over ``batch`` (kept alive in the returned dict):
         params, frame, rays, opts (render precision, stratification draws when perturbing)."""
+        _config.require_64_samples(self.cfg, 'sdf_pdf renderer')
         p = self.params()
         dev = self.device()
         R = batch['ray_o'].shape[1]

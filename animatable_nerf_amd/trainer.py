@@ -294,6 +294,7 @@ class FusedStep:
         return sub, t_rand, a
 
     def step(self, batch, t_rand=None, lr=None):
+        _config.require_64_samples(self.cfg, 'FusedStep.step')
         r = self.renderer
         dev = self.flat.device
         ray_offset = 0

@@ -113,7 +113,7 @@ typedef struct anr_frame {
 } anr_frame;
 
 typedef struct anr_render_opts {
-  int n_samples;     /* cfg.N_samples; only 64 is supported */
+  int n_samples;     /* cfg.N_samples; 64 (anr_render_ns_fwd: 64, 128, 192 or 256) */
   int chunk;         /* rays per reference chunk (2048, tpose_renderer.py:170); semantics depend on it */
   float norm_th;     /* cfg.norm_th (0.05) */
   float train_th;    /* cfg.train_th (0) */
@@ -253,6 +253,29 @@ size_t anr_render_image_workspace_bytes(int n_rays, const anr_render_opts* o, co
 int anr_render_image_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
                          const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
                          const anr_render_out* out, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- render with 64, 128, 192 or 256 samples per ray ------------------------------------------
+ * anr_render_fwd (image_only = 0) and anr_render_image_fwd (image_only != 0) for o->n_samples = 64 k,
+ * k = 1..4 (cfg.N_samples, tpose_renderer.py:26): the same programs, outputs and argument rules, with
+ * raw (R * n_samples, 4), o->t_rand (R, n_samples), sample ids ray * n_samples + sample and the
+ * reference's per-chunk forced argmin / argmax over chunk * n_samples samples. At n_samples = 64 every
+ * output equals the 64-sample entries' bit for bit, and so do the workspace sizes. The visibility
+ * filter, novel_pose, t_rand and the three render precisions work as there.
+ *  Any other n_samples: ANR_E_ARG ("N_samples must be 64, 128, 192 or 256"); the size query returns 0.
+ *  One call takes 24 * n_rays * n_samples < 2^31 (a 512 x 512 frame at 256 samples fits).
+ *  The workspace scales with n_rays * n_samples wherever anr_render_fwd's scales with n_rays * 64; the
+ *    pbw / tbw rows (192 B per sample) dominate the full program's, which the image-only one does not
+ *    have. anr_render_counts works on it (pass any n_rays).
+ *  anr_render_ns_bw_rows / anr_render_ns_row_ids: anr_render_bw_rows / anr_render_row_ids on a full
+ *    (image_only = 0) workspace of this entry; ids are ray * n_samples + sample.
+ *  ANR_E_ARG / ANR_E_WORKSPACE before any HIP call. Training, the animation stage and the sdf_pdf
+ *  programs take 64 samples only. */
+size_t anr_render_ns_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f, int image_only);
+int anr_render_ns_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                      const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                      const anr_render_out* out, int image_only, void* workspace, size_t ws_bytes, void* stream);
+int anr_render_ns_bw_rows(const void* workspace, int n_rays, int n_samples, float* pbw, float* tbw, void* stream);
+int anr_render_ns_row_ids(const void* workspace, int n_rays, int n_samples, int32_t* ids, void* stream);
 
 /* ---- Network.forward over free samples (tpose_nerf_network.py:139-215) ----------------------
  * The call a reference renderer makes per chunk, self.net(wpts, viewdir, dists, batch)
