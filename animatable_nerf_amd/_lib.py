@@ -18,6 +18,7 @@ if os.environ.get('ANR_LIB_PATH'):
 NUM_TENSORS = 46
 NUM_NOVEL_TENSORS = 19
 NUM_SDF_TENSORS = 63
+NUM_LBW_TENSORS = 62
 
 EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_render_workspace_bytes',
            'anr_render_fwd', 'anr_render_counts', 'anr_render_bw_rows', 'anr_render_row_ids', 'anr_profile_enable', 'anr_profile_read', 'anr_profile_read_clock',
@@ -40,6 +41,8 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_mesh_dist_workspace_bytes', 'anr_mesh_sample', 'anr_mesh_point_dist', 'anr_mesh_metrics', 'anr_mesh_order',
            'anr_render_image_workspace_bytes', 'anr_render_image_fwd',
            'anr_render_ns_workspace_bytes', 'anr_render_ns_fwd', 'anr_render_ns_bw_rows', 'anr_render_ns_row_ids',
+           'anr_lbw_render_workspace_bytes', 'anr_lbw_render_fwd', 'anr_lbw_render_counts', 'anr_lbw_render_rows',
+           'anr_lbw_render_knn', 'anr_lbw_render_kept', 'anr_lbw_render_points',
            'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
@@ -124,6 +127,21 @@ class SdfFrame(ctypes.Structure):
 class SdfRenderOut(ctypes.Structure):
     _fields_ = [('rgb_map', ctypes.c_void_p), ('acc_map', ctypes.c_void_p), ('depth_map', ctypes.c_void_p),
                 ('raw', ctypes.c_void_p), ('sdf', ctypes.c_void_p), ('tbounds_out', ctypes.c_void_p)]
+
+
+class LbwParams(ctypes.Structure):
+    _fields_ = [('t', ctypes.c_void_p * NUM_LBW_TENSORS)]
+
+
+class LbwFrame(ctypes.Structure):
+    _fields_ = [('A', ctypes.c_void_p), ('big_A', ctypes.c_void_p), ('R', ctypes.c_void_p), ('Th', ctypes.c_void_p),
+                ('pvertices', ctypes.c_void_p), ('tvertices', ctypes.c_void_p), ('weights', ctypes.c_void_p),
+                ('n_verts', ctypes.c_int), ('tbounds', ctypes.c_void_p), ('latent_index', ctypes.c_void_p)]
+
+
+class LbwRenderOut(ctypes.Structure):
+    _fields_ = [('rgb_map', ctypes.c_void_p), ('acc_map', ctypes.c_void_p), ('depth_map', ctypes.c_void_p),
+                ('raw', ctypes.c_void_p), ('tbounds_out', ctypes.c_void_p)]
 
 
 EVAL_NOUT = 12  # ANR_EVAL_NOUT: doubles of one anr_eval_frame record
@@ -335,6 +353,19 @@ def load():
     lib.anr_mesh_order.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, P, ctypes.c_size_t, P]
     lib.anr_mesh_metrics.argtypes = [P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, P, ctypes.c_int, P, MO, P, P,
                                      ctypes.c_size_t, P]
+    LO = ctypes.POINTER(RenderOpts)
+    lib.anr_lbw_render_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_lbw_render_workspace_bytes.argtypes = [ctypes.c_int, LO, ctypes.c_int]
+    lib.anr_lbw_render_fwd.argtypes = [ctypes.POINTER(LbwParams), ctypes.POINTER(LbwFrame), P, P, P, P, ctypes.c_int, LO,
+                                       ctypes.POINTER(LbwRenderOut), ctypes.c_int, P, ctypes.c_size_t, P]
+    lib.anr_lbw_render_counts.restype = P
+    lib.anr_lbw_render_counts.argtypes = [P, ctypes.c_int, LO, ctypes.c_int]
+    lib.anr_lbw_render_knn.restype = P
+    lib.anr_lbw_render_knn.argtypes = [P, ctypes.c_int, LO, ctypes.c_int]
+    for name in ('anr_lbw_render_kept', 'anr_lbw_render_points'):
+        getattr(lib, name).restype = P
+        getattr(lib, name).argtypes = [P, ctypes.c_int, LO, ctypes.c_int]
+    lib.anr_lbw_render_rows.argtypes = [P, ctypes.c_int, LO, P, P, P, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

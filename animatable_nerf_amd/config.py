@@ -127,6 +127,11 @@ SUBJECTS = {
     # configs/sdf_pdf/anisdf_pdf_s9p.yaml:79-95
     'anisdf_pdf_s9p': {'num_train_frame': 260, 'num_eval_frame': 133, 'H': 1002, 'W': 1000, 'ratio': 1.0,
                        'tpose_viewdir': True, 'use_bigpose': True},
+    # configs/aligned_nerf_lbw/aligned_aninerf_lbw_s9p.yaml:57-93 (network_lbw / renderer_lbw)
+    'aligned_aninerf_lbw_s9p': {'num_train_frame': 260, 'num_eval_frame': 133, 'H': 1002, 'W': 1000, 'ratio': 1.0,
+                                'norm_th': 0.05, 'train_th': 0.0, 'tpose_viewdir': True, 'use_bigpose': True,
+                                'network_module': 'animatable_nerf_amd.network_lbw',
+                                'renderer_module': 'animatable_nerf_amd.renderer_lbw'},
 }
 
 

@@ -287,5 +287,16 @@ int launch_sdfnet(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 int launch_sdfgrad(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 int launch_color(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 __global__ void k_pack_x6(PackArgs a);
+// the aligned_aninerf_lbw render's fused programs (anr_lbw_b16.hip / anr_lbw_x6.hip; anr_mlp_body.h V = 20, 21, 22
+// and + 10), images from k_pack_seq / k_pack_seq_x6 over ANR_L_LBW0, ANR_L_SDF0, ANR_L_LCOL0. MlpArgs of the
+// blend-weight program: ptb / ptb_ld (the point in columns 0..2), fold (layer-0 / layer-5 biases), pbw32 = the
+// init weights ([n][24]), pbw_rows = the softmax output ([n][24]), n_rows. Density: ptb / ptb_ld, y8. Colour:
+// ptb / ptb_ld (a C0 row), y8, fold (lin3's bias at fold + 512), yr.
+__global__ void k_lbw_bw_x6(MlpArgs a);
+__global__ void k_lbw_density_x6(MlpArgs a);
+__global__ void k_lbw_color_x6(MlpArgs a);
+int launch_lbw_bw(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
+int launch_lbw_density(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
+int launch_lbw_color(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 
 }  // namespace anr

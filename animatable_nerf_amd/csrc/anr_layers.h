@@ -152,8 +152,32 @@ __host__ __device__ constexpr LayerDesc color_desc(int l) {
                   : LayerDesc{l, 9 + l, -1, -1, 256, 0, 256, 16, 1, {{SRC_ACT, 64, 0}, {0, 0, 0}}};
 }
 
+// layers 63..71: the aligned_aninerf_lbw blend-weight MLP (aligned_aninerf_lbw_network.py:17-29, 48-58), the
+// shapes of layers 0..8: [gamma_10(x) 63 || bw_latent 128 (folded into the layer-0 / layer-5 biases, k_lbw_fold)]
+// -> 8 x 256 ReLU (skip [features || h] at layer 5, in 447) -> bw_fc 24. Packed as a layer sequence of its own
+// (k_pack_seq): weight of layer 63 + l at t[l], bias at t[9 + l].
+#define ANR_L_LBW0 63
+#define ANR_LBW_LAYERS 9
+__host__ __device__ constexpr LayerDesc lbwbw_desc(int l) {
+  return l == 0   ? LayerDesc{0, 9, -1, -1, 256, 0, 191, 16, 1, {{SRC_EMB, 16, 0}, {0, 0, 0}}}
+         : l == 5 ? LayerDesc{5, 14, -1, -1, 256, 0, 447, 16, 2, {{SRC_EMB, 16, 0}, {SRC_ACT, 64, 191}}}
+         : l == 8 ? LayerDesc{8, 17, -1, -1, 24, 0, 256, 2, 1, {{SRC_ACT, 64, 0}, {0, 0, 0}}}
+                  : LayerDesc{l, 9 + l, -1, -1, 256, 0, 256, 16, 1, {{SRC_ACT, 64, 0}, {0, 0, 0}}};
+}
+
+// layers 72..76: the aligned_aninerf_lbw colour network (aligned_aninerf_lbw_network.py:355-436, mode idr without
+// a normal): lin0 on [points 3 || gamma_4(dir) 27] (a C0 row, SRC_G0) || feature 256 (SRC_G1), 286 inputs; lin1..lin4
+// as the sdf_pdf colour network's.
+#define ANR_L_LCOL0 72
+#define ANR_LCOL_LAYERS 5
+__host__ __device__ constexpr LayerDesc lbwcol_desc(int l) {
+  return l == 0 ? LayerDesc{0, 9, -1, -1, 256, 0, 286, 16, 2, {{SRC_G0, 16, 0, 30}, {SRC_G1, 64, 30}}} : color_desc(l);
+}
+
 __host__ __device__ constexpr LayerDesc layer_desc_all(int i) {
-  return i >= ANR_L_COL0 ? color_desc(i - ANR_L_COL0)
+  return i >= ANR_L_LCOL0 ? lbwcol_desc(i - ANR_L_LCOL0)
+       : i >= ANR_L_LBW0 ? lbwbw_desc(i - ANR_L_LBW0)
+       : i >= ANR_L_COL0 ? color_desc(i - ANR_L_COL0)
        : i >= ANR_L_SREV0 ? sdfrev_desc(i - ANR_L_SREV0)
        : i >= ANR_L_SDF0 ? sdfnet_desc(i - ANR_L_SDF0)
        : i >= ANR_L_RESD0 ? resd_desc(i - ANR_L_RESD0)

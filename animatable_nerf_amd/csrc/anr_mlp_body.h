@@ -94,21 +94,27 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 //         pose-space BW MLP, 9..16 the NeRF trunk (layers 9..16), 17 the folded colour head
 //         (ANR_L_HEAD), 18 rgb_fc. V = 19 (k_mlp_img_x6): the same program with every entry in mode 2.
 template <int V>
-__host__ __device__ constexpr int prog_base() { return V >= 10 ? V - 10 : V; }
+__host__ __device__ constexpr int prog_base() { return V >= 30 ? V - 10 : V >= 20 ? V : V >= 10 ? V - 10 : V; }
+// the bf16x6 (fp32-level) form of a program: V + 10 of its base (bases 0..9 and 20..29)
+template <int V>
+__host__ __device__ constexpr bool prog_x6() { return prog_base<V>() != V; }
 template <int V>
 __host__ __device__ constexpr int prog_len() {
   constexpr int B = prog_base<V>();
-  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5) ? 9 : B == 7 ? 8 : B == 6 ? 5 : B == 9 ? 19 : 18;  // 1, 8: 18
+  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5 || B == 20 || B == 21) ? 9 : B == 7 ? 8 : (B == 6 || B == 22) ? 5 : B == 9 ? 19 : 18;  // 1, 8: 18
 }
 // programs whose weights are a packed layer sequence of their own (k_pack_seq), not the render image
 template <int V>
 __host__ __device__ constexpr bool prog_seq() {
-  return prog_base<V>() == 3 || prog_base<V>() == 5 || prog_base<V>() == 6 || prog_base<V>() == 7;
+  return prog_base<V>() == 3 || prog_base<V>() == 5 || prog_base<V>() == 6 || prog_base<V>() == 7 || prog_base<V>() >= 20;
 }
 template <int V>
 __host__ __device__ constexpr int prog_layer(int e) {
-  if (V >= 10) return prog_layer<prog_base<V>()>(e);
+  if (prog_x6<V>()) return prog_layer<prog_base<V>()>(e);
   return V == 3 ? ANR_L_RESD0 + e
+         : V == 20 ? ANR_L_LBW0 + e
+         : V == 21 ? ANR_L_SDF0 + e
+         : V == 22 ? ANR_L_LCOL0 + e
          : V == 5 ? ANR_L_SDF0 + e
          : V == 7 ? ANR_L_SREV0 + e
          : V == 6 ? ANR_L_COL0 + e
@@ -122,7 +128,7 @@ __host__ __device__ constexpr int prog_layer(int e) {
 __host__ __device__ constexpr bool prog_pose(int e) { return e < 9; }
 template <bool B16, int V>
 __host__ __device__ constexpr int prog_mode(int e) {
-  return B16 ? ((V == 4 || V == 8 || V >= 10) ? 2 : e < 9 ? ANR_POSE_MODE : 1) : 0;
+  return B16 ? ((V == 4 || V == 8 || prog_x6<V>()) ? 2 : (e < 9 && V < 20) ? ANR_POSE_MODE : 1) : 0;
 }
 // Slices = the staging unit: mode 0 8 fp32 k-steps; mode 1 one 32-input k-step (OB x 2 KiB);
 // mode 2 one 32-input k-step of a group of <= 8 out-blocks (x 3 KiB).
@@ -438,6 +444,9 @@ static_assert(prog_bias_off<5>(prog_len<5>()) <= ANR_BIAS_TABLE_FLOATS, "bias ta
 static_assert(prog_bias_off<7>(prog_len<7>()) == seq_bias_off(ANR_L_SREV0, ANR_SREV_LAYERS), "sdf grad bias section");
 static_assert(prog_bias_off<6>(prog_len<6>()) == seq_bias_off(ANR_L_COL0, ANR_COL_LAYERS), "colour bias section");
 static_assert(prog_bias_off<7>(prog_len<7>()) + 256 <= ANR_BIAS_TABLE_FLOATS, "bias table + W8 row (anr_layers.h)");
+static_assert(prog_bias_off<20>(prog_len<20>()) == seq_bias_off(ANR_L_LBW0, ANR_LBW_LAYERS), "lbw blend-weight bias section");
+static_assert(prog_bias_off<22>(prog_len<22>()) == seq_bias_off(ANR_L_LCOL0, ANR_LCOL_LAYERS), "lbw colour bias section");
+static_assert(prog_bias_off<20>(prog_len<20>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
 
 // Fill the bias table once per launch (before the first barrier of the slice stream). Sources:
 // the packed bias section, the novel_pose_bw copy for the pose pass (pose_boff), and the per-frame
@@ -452,11 +461,11 @@ __device__ __forceinline__ void fill_bias_table(const MlpArgs& a, float* __restr
     constexpr int toff = prog_bias_off<V>(e);
     const float* src;
     constexpr int VB = prog_base<V>();
-    if constexpr (VB == 3) {  // sdf residual MLP: poses folded into layers 0 / 5 (k_sdf_fold)
+    if constexpr (VB == 3 || VB == 20) {  // sdf residual MLP / lbw blend-weight MLP: folds of layers 0 / 5
       src = e == 0 ? a.fold : e == 5 ? a.fold + 256 : a.bias + toff;
-    } else if constexpr (VB == 5 || VB == 7) {  // sdf network (forward / gradient): the image's bias section
+    } else if constexpr (VB == 5 || VB == 7 || VB == 21) {  // sdf network (forward / gradient): the image's bias section
       src = a.bias + toff;
-    } else if constexpr (VB == 6) {  // colour network: color_latent folded into lin3 (k_sdf_fold)
+    } else if constexpr (VB == 6 || VB == 22) {  // colour network: color_latent folded into lin3 (k_sdf_fold)
       src = e == 3 ? a.fold + 512 : a.bias + toff;
     } else if constexpr (e < 9) {
       src = L == 0 ? a.fold + 0 : L == 5 ? a.fold + 512 : a.bias + a.pose_boff + boff;
@@ -552,7 +561,7 @@ __device__ __forceinline__ float softplus100_fac(float x, float& fac) {
 }
 template <int V>
 __device__ __forceinline__ float sp_fwd(float x) {
-  static_assert(V < 10, "the fp32-level programs use softplus100_fac");
+  static_assert(!prog_x6<V>(), "the fp32-level programs use softplus100_fac");
   return softplus100(x);
 }
 
@@ -1567,9 +1576,9 @@ __device__ __forceinline__ void softplus_regs(f32x4 (&v)[17]) {
 // (Y8 columns 8..263: 16-B aligned for k_color_b16's row loads). bf16x6 (V = 15) writes the backward
 // factors sigmoid(100 z) in those slots instead (lin3's unscaled in X4[:, :217]): softplus100_fac
 // gives them beside h, and the reverse pass then multiplies without recomputing them.
-template <bool X6>
-__device__ __forceinline__ void sdfnet_body(const MlpArgs& a) {
-  constexpr int V = 5 + (X6 ? 10 : 0);
+template <int V, bool STORE>
+__device__ __forceinline__ void sdfnet_prog(const MlpArgs& a) {
+  constexpr bool X6 = prog_x6<V>();
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1607,7 +1616,7 @@ __device__ __forceinline__ void sdfnet_body(const MlpArgs& a) {
     };
     // each layer's softplus runs in the next layer's split (SP_IN), which also stores its h
     // store targets formed at each call (a per-tile array of row pointers costs 16 VGPRs for the tile)
-    auto st = [&](int i) { return LayerIO{valid ? (i == 3 ? a.x4 : a.sdf_h[i]) + row * 256 : nullptr}; };
+    auto st = [&](int i) { return LayerIO{STORE && valid ? (i == 3 ? a.x4 : a.sdf_h[i]) + row * 256 : nullptr}; };
     f32x4 dummy[1];
     layer<true, V, 0, false>(p, dummy, emb, vemb, A, sb, g, lane);
     layer<true, V, 1, false, false, 1>(p, A, emb, vemb, B, sb, g, lane, st(0));
@@ -1619,17 +1628,18 @@ __device__ __forceinline__ void sdfnet_body(const MlpArgs& a) {
     layer<true, V, 6, false, false, 1>(p, B, emb, vemb, A, sb, g, lane, st(5));
     layer<true, V, 7, false, false, 1>(p, A, emb, vemb, B, sb, g, lane, st(6));
     if constexpr (X6) {  // h7 in place for lin8, its backward factors to sdf_h[7]
-      float* d = a.sdf_h[7] + row * 256 + 4 * g;
+      float* d = STORE ? a.sdf_h[7] + row * 256 + 4 * g : nullptr;
       static_for<0, 16>([&](auto ob) {
         constexpr int o = decltype(ob)::value;
         float f[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) B[o][r] = softplus100_fac(B[o][r], f[r]);
-        if (valid) *(f32x4*)(d + 16 * o) = f32x4{f[0], f[1], f[2], f[3]};
+        if constexpr (STORE)
+          if (valid) *(f32x4*)(d + 16 * o) = f32x4{f[0], f[1], f[2], f[3]};
       });
     } else {
       softplus_regs<16, V>(B);  // lin8 (a tail-slice layer, not streamed) reads h7 as is
-      store_h(B, a.sdf_h[7]);
+      if constexpr (STORE) store_h(B, a.sdf_h[7]);
     }
     layer<true, V, 8, false>(p, B, emb, vemb, A, sb, g, lane);  // [sdf || feature], no activation
     if (valid) {  // sdf (neuron 0) to column 0, the feature (neurons 1..256) to columns 8..263
@@ -1737,9 +1747,8 @@ __device__ __forceinline__ void sdfgrad_body(const MlpArgs& a) {
 // SDF net's feature from its Y8 row (columns 8..263, written there by k_sdfnet_b16), then
 // lin1..lin3 (ReLU deferred into the next split, the colour latent folded into lin3's bias), lin4's
 // three logits to yr ([n][4]); k_sdf_raw applies the sigmoid.
-template <bool X6>
-__device__ __forceinline__ void color_body(const MlpArgs& a) {
-  constexpr int V = 6 + (X6 ? 10 : 0);
+template <int V>
+__device__ __forceinline__ void color_prog(const MlpArgs& a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -1779,6 +1788,89 @@ __device__ __forceinline__ void color_body(const MlpArgs& a) {
       y[0] = A[0][0];
       y[1] = A[0][1];
       y[2] = A[0][2];
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the last (unused) prefetch
+}
+
+// the sdf_pdf programs V = 5 / 15 (every softplus output or factor stored for the reverse pass) and 6 / 16
+template <bool X6>
+__device__ __forceinline__ void sdfnet_body(const MlpArgs& a) { sdfnet_prog<5 + (X6 ? 10 : 0), true>(a); }
+template <bool X6>
+__device__ __forceinline__ void color_body(const MlpArgs& a) { color_prog<6 + (X6 ? 10 : 0)>(a); }
+
+// aligned_aninerf_lbw programs (anr_lbw_b16.hip / anr_lbw_x6.hip; driven by anr_lbw_capi.hip):
+//   V = 21 / 31 density forward: NeRFNetwork.forward (aligned_aninerf_lbw_network.py:336-352) = the layers of V = 5
+//       from the same packed sequence, with no per-layer store (no gradient pass reads them): [density || feature]
+//       to y8 in V = 5's layout.
+//   V = 22 / 32 colour: ColorNetwork.forward (:403-436), lin0 on 30 + 256 inputs (no normal).
+template <bool X6>
+__device__ __forceinline__ void lbw_density_body(const MlpArgs& a) { sdfnet_prog<21 + (X6 ? 10 : 0), false>(a); }
+template <bool X6>
+__device__ __forceinline__ void lbw_color_body(const MlpArgs& a) { color_prog<22 + (X6 ? 10 : 0)>(a); }
+
+//   V = 20 / 30 blend weights: calculate_neural_blend_weights (:48-58) per kept sample of one batch, on chip —
+//       gamma_10 of the point (ptb rows, xyz in columns 0..2), 8 x 256 ReLU layers (bw_latent folded into the
+//       layer-0 / layer-5 biases: fold[0..512)), bw_fc, then softmax(log(init + 1e-9) + y) over the 24 joints with
+//       init read per row from pbw32 ([n][24]); the weights go to pbw_rows ([n][24]). A row's 24 logits sit in
+//       its four lanes (neuron 16 o + 4 g + r in lane group g): maximum and sum cross them by two shuffles.
+template <bool X6>
+__device__ __forceinline__ void lbw_bw_body(const MlpArgs& a) {
+  constexpr int V = 20 + (X6 ? 10 : 0);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4;
+  const int pl = lane & 15;
+  float* sb = (float*)smem;  // bias table (anr_layers.h LDS layout)
+  fill_bias_table<V>(a, sb, tid);
+  const int n = a.n_rows;
+  const int ntiles = (n + 127) / 128;
+  if ((int)blockIdx.x >= ntiles) return;  // uniform per workgroup, before any LDS-DMA
+
+  Pipe p{smem + mlp_ring_off(), mlp_slice_max<true>(), mlp_nbuf<true>(), a.wimg, 0, wave, lane, 0};
+  p.template start<true, V>();
+
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int idx = tile * 128 + wave * 16 + pl;
+    const bool valid = idx < n;
+    const size_t row = (size_t)(valid ? idx : n - 1);
+    const float* pt = a.ptb + row * a.ptb_ld;
+    const float x[3] = {pt[0], pt[1], pt[2]};
+    float emb[16], vemb[8];
+    f32x4 A[17], B[17], fc[2];
+    embed_b<2>(x, g, 10, emb);
+#pragma unroll
+    for (int s8 = 0; s8 < 8; ++s8) vemb[s8] = 0.f;
+    bw_mlp<true, V, 0>(p, emb, vemb, sb, A, B, fc, g, lane);
+    // this lane's joints: 4 g + r (o = 0) and, for g < 2, 16 + 4 g + r (o = 1)
+    const float* init = a.pbw32 + row * 24;
+    const bool two = g < 2;
+    const f32x4 i0 = *(const f32x4*)(init + 4 * g);
+    const f32x4 i1 = two ? *(const f32x4*)(init + 16 + 4 * g) : f32x4{1.f, 1.f, 1.f, 1.f};
+    float v[8];
+    float m = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      v[r] = logf(i0[r] + 1e-9f) + fc[0][r];
+      v[4 + r] = two ? logf(i1[r] + 1e-9f) + fc[1][r] : -INFINITY;
+      m = fmaxf(m, fmaxf(v[r], v[4 + r]));
+    }
+    m = fmaxf(m, __shfl_xor(m, 16));
+    m = fmaxf(m, __shfl_xor(m, 32));
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+      v[r] = expf(v[r] - m);  // exp(-inf) = 0 at the joints this lane does not hold
+      s += v[r];
+    }
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (valid) {
+      float* out = a.pbw_rows + row * 24;
+      *(f32x4*)(out + 4 * g) = f32x4{v[0] / s, v[1] / s, v[2] / s, v[3] / s};
+      if (two) *(f32x4*)(out + 16 + 4 * g) = f32x4{v[4] / s, v[5] / s, v[6] / s, v[7] / s};
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the last (unused) prefetch

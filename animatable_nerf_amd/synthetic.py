@@ -343,6 +343,23 @@ def init_state_dict_sdf(shapes, seed=4321):
     return {n: out[n] for n in names}
 
 
+def init_state_dict_lbw(shapes, seed=8642):
+    """Deterministic weights for the aligned_aninerf_lbw network (``aligned_aninerf_lbw_network.py``), per
+    tensor a PCG64 stream seeded with (seed, index), by the recipe of ``init_state_dict_sdf``:
+
+      * ``nerf_network.lin*``: the geometric init of ``aligned_aninerf_lbw_network.py:302-323`` at the
+        reference's scale (output 0 ~ |x| - 0.5, so the density relu(y0) is positive on part of the kept
+        samples and zero on the rest), hidden biases U(+-0.01);
+      * the colour net's ``weight_v`` and biases U(+-1/sqrt(in)); every ``weight_g`` = row norm of its
+        ``weight_v`` times U(0.8, 1.2);
+      * Conv1d (``bw_linears`` / ``bw_fc``, ``novel_pose_bw.*`` when present) U(+-1/sqrt(fan_in));
+        embeddings N(0,1).
+    """
+    alias = {n: n.replace('nerf_network', 'sdf_network') for n in shapes}
+    sd = init_state_dict_sdf({alias[n]: s for n, s in shapes.items()}, seed=seed)
+    return {n: sd[alias[n]] for n in shapes}
+
+
 def init_state_dict(shapes, seed=1234, alpha_bias=3.0):
     """Deterministic weights for a state_dict given {name: shape} (insertion order matters).
 

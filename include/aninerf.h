@@ -774,6 +774,88 @@ int anr_mesh_metrics(const float* src_verts, int src_nv, const int32_t* src_face
                      int tgt_nv, const int32_t* tgt_faces, int tgt_nf, const double* u, const anr_meshdist_opts* o,
                      double* out, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- aligned_aninerf_lbw variant (aligned_aninerf_lbw_network.py; the configs/aligned_nerf_lbw yamls) ---
+ * The KNN-skinned NeRF of the extended paper, eval (no-grad) whole-frame render under tpose_renderer.render
+ * (:159-186, Network.forward :90-147 per 2048-ray chunk): 5-NN blend over pvertices with the keep mask
+ * pnorm < o->norm_th (cfg.norm_th, 0.05) + the chunk's argmin, the pose-space blend-weight MLP with
+ * bw_latent[latent_index + 1], LBS pose -> T -> big pose for points and view directions (tpose_viewdir), a
+ * second 5-NN blend of the warped points over tvertices and the same MLP with bw_latent[0] (tbw), the
+ * weight-normed softplus(beta 100) density net, alpha = 1 - exp(-relu(y0) dist), the IDR colour net without a
+ * normal (286 inputs), raw zeroed outside tbounds widened in place by 0.05 per chunk, the alpha_ind rows
+ * (alpha > o->train_th + the chunk's argmax) of pbw / tbw, raw2outputs.
+ * Parameters: the 62 tensors of aligned_aninerf_lbw_network.Network's state_dict, in order (a checkpoint's
+ * novel_pose_bw.* tensors, present under cfg.aninerf_animation, follow them and are not read):
+ *   0..26  tpose_human.nerf_network.lin{0..8}.{bias, weight_g (o,1), weight_v (o,i)}
+ *          i/o: 39/256, 256/256, 256/256, 256/217, 256/256 x4, 256/257
+ *   27     tpose_human.color_network.color_latent.weight (L,128)
+ *   28..42 tpose_human.color_network.lin{0..4}.{bias, weight_g, weight_v}  i: 286,256,256,384,256
+ *   43     bw_latent.weight (num_train_frame + 1, 128)
+ *   44..59 bw_linears.{0..7}.{weight,bias}      Conv1d, in: 191,256,256,256,256,447,256,256
+ *   60,61  bw_fc.{weight,bias} (24,256,1)
+ * Precisions: ANR_FP32 (exact fp32 MFMA layer products as layer GEMMs, the parity anchor; the environment switch
+ * ANR_SDF_LG32=0 of the sdf_pdf render moves them from k_lgemm to k_gemm here too), ANR_BF16X3 and ANR_BF16X6 (the
+ * blend-weight MLP with its log-softmax epilogue, the density net and the colour net as one fused launch per batch
+ * each, split bf16 with 3 products or, fp32-level, 6).
+ * Not covered (ANR_E_ARG where an option would ask for it): training / autograd, cfg.test_novel_pose
+ * (o->novel_pose), get_alpha / mesh extraction, the mmsk visibility filter, Network.forward over free
+ * samples, N_samples != 64, cfg.tpose_viewdir False, color_with_viewdir False.
+ * The KNN boundary is unpinned as for sdf_pdf: pytorch3d knn_points is restated, not run (k_sdf_front). */
+#define ANR_LBW_NUM_TENSORS 62
+
+typedef struct anr_lbw_params {
+  const float* t[ANR_LBW_NUM_TENSORS];  /* device pointers, state_dict order above */
+} anr_lbw_params;
+
+typedef struct anr_lbw_frame {
+  const float* A;          /* (24,4,4) device */
+  const float* big_A;      /* (24,4,4) device: big pose */
+  const float* R;          /* (3,3) */
+  const float* Th;         /* (3) */
+  const float* pvertices;  /* (V,3) posed SMPL vertices in the pose frame, V <= 6912 */
+  const float* tvertices;  /* (V,3) big-pose SMPL vertices (NULL allowed for an image-only call) */
+  const float* weights;    /* (V,24) skin weights */
+  int n_verts;
+  const float* tbounds;    /* (2,3) batch['tbounds'] as passed in */
+  const int64_t* latent_index;  /* (1): colour latent row; bw_latent row latent_index + 1 */
+} anr_lbw_frame;
+
+typedef struct anr_lbw_render_out {
+  float* rgb_map;      /* (R,3) */
+  float* acc_map;      /* (R) */
+  float* depth_map;    /* (R) */
+  float* raw;          /* (R*64,4) */
+  float* tbounds_out;  /* (2,3) or NULL: batch['tbounds'] after the in-place widening by 0.05 per chunk (:124-126) */
+} anr_lbw_render_out;
+
+/* Asynchronous on the caller's stream except for one host read of the kept-sample count (it sizes the layer
+ * GEMMs); allocates nothing. image_only != 0 (cfg.render_image_only): no second search, no T-pose blend-weight
+ * MLP, no alpha_ind rows -- no rendered map depends on them, and raw and the maps equal the full call's bit for
+ * bit; anr_lbw_render_rows then has nothing to return and counts[1] is 0.
+ * ANR_E_ARG / ANR_E_WORKSPACE before any HIP call for: a NULL pointer, n_verts outside 1..6912,
+ * o->n_samples != 64, o->novel_pose, a precision other than ANR_FP32 / ANR_BF16X3 / ANR_BF16X6, a workspace smaller than
+ * anr_lbw_render_workspace_bytes(n_rays, o, image_only) (which makes no HIP call; 0 for bad arguments).
+ * Kept samples run in batches of at most 2^18 rows (the environment variable ANR_LBW_BATCH, a multiple of
+ * 256, overrides the batch size for tests; it must hold the same value for the size query and the call). */
+size_t anr_lbw_render_workspace_bytes(int n_rays, const anr_render_opts* o, int image_only);
+int anr_lbw_render_fwd(const anr_lbw_params* p, const anr_lbw_frame* f, const float* ray_o, const float* ray_d,
+                       const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                       const anr_lbw_render_out* out, int image_only, void* workspace, size_t ws_bytes, void* stream);
+/* device int32[2] inside the workspace: {kept samples n', alpha_ind rows m}. */
+const int32_t* anr_lbw_render_counts(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+/* copy the alpha_ind rows pbw (m,24), tbw (m,24) and / or their sample ids (m; ray * 64 + sample) out of the
+ * workspace of a full (not image-only) call; NULL outputs are skipped */
+int anr_lbw_render_rows(const void* workspace, int n_rays, const anr_render_opts* o, float* pbw, float* tbw,
+                        int32_t* ids, void* stream);
+/* device uint32 (R*64, 8) inside the workspace: the first search's per-sample KNN records, as
+ * anr_sdf_render_knn -- a debugging / test view of the knn_points boundary. */
+const uint32_t* anr_lbw_render_knn(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+/* two more test views into the workspace of the last call (unstable: they follow the workspace layout, not a
+ * contract; for tests and debugging only): the kept sample ids (n' int32, ray * 64 + sample, in
+ * order), and the colour-net input rows of the last batch of kept samples ((rows, 40) floats: the warped point
+ * in columns 0..2, the warped view direction in 3..5). */
+const int32_t* anr_lbw_render_kept(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+const float* anr_lbw_render_points(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+
 /* ---- measurement ----------------------------------------------------------------------
  * When enabled, anr_render_fwd records a hipEvent pair around the fused network kernel (k_mlp)
  * on the caller's stream, and anr_sdf_render_fwd one around each fused sdf_pdf network launch. anr_profile_read waits for the recorded events, returns the summed
