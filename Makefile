@@ -12,7 +12,8 @@ SRCS := $(SRC_DIR)/anr_capi.hip $(SRC_DIR)/anr_rays.hip $(SRC_DIR)/anr_mlp.hip $
         $(SRC_DIR)/anr_mlp_img.hip $(SRC_DIR)/anr_mlp_img_b16.hip $(SRC_DIR)/anr_mlp_img_x6.hip \
         $(SRC_DIR)/anr_rays_ns.hip $(SRC_DIR)/anr_mlp_ns.hip $(SRC_DIR)/anr_mlp_b16_ns.hip $(SRC_DIR)/anr_mlp_x6_ns.hip \
         $(SRC_DIR)/anr_mlp_img_ns.hip $(SRC_DIR)/anr_mlp_img_b16_ns.hip $(SRC_DIR)/anr_mlp_img_x6_ns.hip \
-        $(SRC_DIR)/anr_lbw.hip $(SRC_DIR)/anr_lbw_capi.hip $(SRC_DIR)/anr_lbw_b16.hip $(SRC_DIR)/anr_lbw_x6.hip
+        $(SRC_DIR)/anr_lbw.hip $(SRC_DIR)/anr_lbw_capi.hip $(SRC_DIR)/anr_lbw_b16.hip $(SRC_DIR)/anr_lbw_x6.hip \
+        $(SRC_DIR)/anr_pdf.hip $(SRC_DIR)/anr_pdf_capi.hip $(SRC_DIR)/anr_pdf_b16.hip $(SRC_DIR)/anr_pdf_x6.hip
 OBJS := $(SRCS:.hip=.o)
 DEPS := $(OBJS:.o=.d)
 LIB := animatable_nerf_amd/libaninerf_hip.so
@@ -39,7 +40,7 @@ $(TESTLIB): $(OBJS) $(TESTOBJ)
 # v_pk_add_f32, which costs more issue cycles beside MFMAs than two v_sub_f32 (same-box A/B round 6:
 # sdf_pdf bf16x6 frame 180.0 -> 175.8 ms, k_mlp_x6 cycles -2.4 %, profiles/round6/r8b_*)
 $(SRC_DIR)/anr_mlp_x6.o $(SRC_DIR)/anr_resd_x6.o $(SRC_DIR)/anr_mlp_img_x6.o: CXXFLAGS += -fno-slp-vectorize
-$(SRC_DIR)/anr_mlp_x6_ns.o $(SRC_DIR)/anr_mlp_img_x6_ns.o $(SRC_DIR)/anr_lbw_x6.o: CXXFLAGS += -fno-slp-vectorize
+$(SRC_DIR)/anr_mlp_x6_ns.o $(SRC_DIR)/anr_mlp_img_x6_ns.o $(SRC_DIR)/anr_lbw_x6.o $(SRC_DIR)/anr_pdf_x6.o: CXXFLAGS += -fno-slp-vectorize
 
 $(LIB): $(OBJS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@.tmp $(OBJS) && mv -f $@.tmp $@
@@ -55,6 +56,9 @@ resources: $(SRC_DIR)/anr_mlp.hip $(SRC_DIR)/anr_mlp_b16.hip
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_lbw.hip -o /tmp/anr_lbw_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_lbw_b16.hip -o /tmp/anr_lbw_b16_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -fno-slp-vectorize -c $(SRC_DIR)/anr_lbw_x6.hip -o /tmp/anr_lbw_x6_res.o -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_pdf.hip -o /tmp/anr_pdf_res.o -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_pdf_b16.hip -o /tmp/anr_pdf_b16_res.o -Rpass-analysis=kernel-resource-usage
+	$(HIPCC) $(CXXFLAGS) -fno-slp-vectorize -c $(SRC_DIR)/anr_pdf_x6.hip -o /tmp/anr_pdf_x6_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -c $(SRC_DIR)/anr_resd_b16.hip -o /tmp/anr_resd_b16_res.o -Rpass-analysis=kernel-resource-usage
 	$(HIPCC) $(CXXFLAGS) -fno-slp-vectorize -c $(SRC_DIR)/anr_resd_x6.hip -o /tmp/anr_resd_x6_res.o -Rpass-analysis=kernel-resource-usage
 	for u in anr_mlp_ns anr_mlp_b16_ns anr_mlp_img_ns anr_mlp_img_b16_ns; do \

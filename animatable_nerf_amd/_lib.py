@@ -19,6 +19,7 @@ NUM_TENSORS = 46
 NUM_NOVEL_TENSORS = 19
 NUM_SDF_TENSORS = 63
 NUM_LBW_TENSORS = 62
+NUM_PDF_TENSORS = 62
 
 EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_render_workspace_bytes',
            'anr_render_fwd', 'anr_render_counts', 'anr_render_bw_rows', 'anr_render_row_ids', 'anr_profile_enable', 'anr_profile_read', 'anr_profile_read_clock',
@@ -43,6 +44,9 @@ EXPORTS = ('anr_near_far', 'anr_params_packed_bytes', 'anr_params_pack', 'anr_re
            'anr_render_ns_workspace_bytes', 'anr_render_ns_fwd', 'anr_render_ns_bw_rows', 'anr_render_ns_row_ids',
            'anr_lbw_render_workspace_bytes', 'anr_lbw_render_fwd', 'anr_lbw_render_counts', 'anr_lbw_render_rows',
            'anr_lbw_render_knn', 'anr_lbw_render_kept', 'anr_lbw_render_points',
+           'anr_pdf_render_workspace_bytes', 'anr_pdf_render_fwd', 'anr_pdf_render_counts', 'anr_pdf_render_rows',
+           'anr_pdf_render_knn', 'anr_pdf_render_kept', 'anr_pdf_render_points', 'anr_pdf_render_bigpose',
+           'anr_pdf_alpha_workspace_bytes', 'anr_pdf_alpha_points',
            'anr_last_error', 'anr_version')
 
 c_float_p = ctypes.c_void_p
@@ -140,6 +144,23 @@ class LbwFrame(ctypes.Structure):
 
 
 class LbwRenderOut(ctypes.Structure):
+    _fields_ = [('rgb_map', ctypes.c_void_p), ('acc_map', ctypes.c_void_p), ('depth_map', ctypes.c_void_p),
+                ('raw', ctypes.c_void_p), ('tbounds_out', ctypes.c_void_p)]
+
+
+class PdfParams(ctypes.Structure):
+    _fields_ = [('t', ctypes.c_void_p * NUM_PDF_TENSORS)]
+
+
+class PdfFrame(ctypes.Structure):
+    _fields_ = [('A', ctypes.c_void_p), ('big_A', ctypes.c_void_p), ('R', ctypes.c_void_p), ('Th', ctypes.c_void_p),
+                ('pvertices', ctypes.c_void_p), ('weights', ctypes.c_void_p), ('poses', ctypes.c_void_p),
+                ('tbounds', ctypes.c_void_p), ('latent_index', ctypes.c_void_p), ('n_verts', ctypes.c_int),
+                ('n_views', ctypes.c_int), ('Ks', ctypes.c_void_p), ('RT', ctypes.c_void_p), ('msks', ctypes.c_void_p),
+                ('img_h', ctypes.c_int), ('img_w', ctypes.c_int)]
+
+
+class PdfRenderOut(ctypes.Structure):
     _fields_ = [('rgb_map', ctypes.c_void_p), ('acc_map', ctypes.c_void_p), ('depth_map', ctypes.c_void_p),
                 ('raw', ctypes.c_void_p), ('tbounds_out', ctypes.c_void_p)]
 
@@ -366,6 +387,19 @@ def load():
         getattr(lib, name).restype = P
         getattr(lib, name).argtypes = [P, ctypes.c_int, LO, ctypes.c_int]
     lib.anr_lbw_render_rows.argtypes = [P, ctypes.c_int, LO, P, P, P, P]
+    lib.anr_pdf_render_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_pdf_render_workspace_bytes.argtypes = [ctypes.c_int, LO, ctypes.c_int]
+    lib.anr_pdf_render_fwd.argtypes = [ctypes.POINTER(PdfParams), ctypes.POINTER(PdfFrame), P, P, P, P, ctypes.c_int, LO,
+                                       ctypes.POINTER(PdfRenderOut), ctypes.c_int, P, ctypes.c_size_t, P]
+    for name in ('anr_pdf_render_counts', 'anr_pdf_render_knn', 'anr_pdf_render_kept', 'anr_pdf_render_points',
+                 'anr_pdf_render_bigpose'):
+        getattr(lib, name).restype = P
+        getattr(lib, name).argtypes = [P, ctypes.c_int, LO, ctypes.c_int]
+    lib.anr_pdf_render_rows.argtypes = [P, ctypes.c_int, LO, P, P, P]
+    lib.anr_pdf_alpha_workspace_bytes.restype = ctypes.c_size_t
+    lib.anr_pdf_alpha_workspace_bytes.argtypes = [ctypes.c_long, ctypes.POINTER(AlphaOpts)]
+    lib.anr_pdf_alpha_points.argtypes = [ctypes.POINTER(PdfParams), ctypes.POINTER(PdfFrame), P, ctypes.c_long,
+                                         ctypes.POINTER(AlphaOpts), P, P, ctypes.c_size_t, P]
     lib.anr_last_error.restype = ctypes.c_char_p
     for name in EXPORTS:
         getattr(lib, name)

@@ -132,6 +132,12 @@ SUBJECTS = {
                                 'norm_th': 0.05, 'train_th': 0.0, 'tpose_viewdir': True, 'use_bigpose': True,
                                 'network_module': 'animatable_nerf_amd.network_lbw',
                                 'renderer_module': 'animatable_nerf_amd.renderer_lbw'},
+    # configs/aligned_nerf_pdf/aligned_aninerf_pdf_s9p.yaml:57-98 (network_pdf / renderer_pdf; the network's keep
+    # threshold is its own hard-coded 0.1, not norm_th)
+    'aligned_aninerf_pdf_s9p': {'num_train_frame': 260, 'num_eval_frame': 133, 'H': 1002, 'W': 1000, 'ratio': 1.0,
+                                'norm_th': 0.05, 'train_th': 0.0, 'tpose_viewdir': True, 'use_bigpose': True,
+                                'network_module': 'animatable_nerf_amd.network_pdf',
+                                'renderer_module': 'animatable_nerf_amd.renderer_pdf'},
 }
 
 

@@ -298,5 +298,11 @@ __global__ void k_lbw_color_x6(MlpArgs a);
 int launch_lbw_bw(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 int launch_lbw_density(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 int launch_lbw_color(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
+// the aligned_aninerf_pdf render's fused displacement program (anr_pdf_b16.hip / anr_pdf_x6.hip; anr_mlp_body.h
+// V = 23 / 33), image from k_pack_seq / k_pack_seq_x6 over ANR_L_RESD0 as k_resd_*'s. MlpArgs: ptb / ptb_ld (the
+// big-pose point in columns 0..2), fold (layer-0 / layer-5 biases), yr = the batch's compact resd rows ([n][3], or
+// NULL), gb = the colour / density input rows ([n][40]: tpose to columns 0..2), n_rows.
+__global__ void k_pdf_resd_x6(MlpArgs a);
+int launch_pdf_resd(const MlpArgs& a, int grid, hipStream_t s, bool x6 = false);
 
 }  // namespace anr

@@ -101,7 +101,7 @@ __host__ __device__ constexpr bool prog_x6() { return prog_base<V>() != V; }
 template <int V>
 __host__ __device__ constexpr int prog_len() {
   constexpr int B = prog_base<V>();
-  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5 || B == 20 || B == 21) ? 9 : B == 7 ? 8 : (B == 6 || B == 22) ? 5 : B == 9 ? 19 : 18;  // 1, 8: 18
+  return B == 0 ? 30 : (B == 2 || B == 4) ? 28 : (B == 3 || B == 5 || B == 20 || B == 21 || B == 23) ? 9 : B == 7 ? 8 : (B == 6 || B == 22) ? 5 : B == 9 ? 19 : 18;  // 1, 8: 18
 }
 // programs whose weights are a packed layer sequence of their own (k_pack_seq), not the render image
 template <int V>
@@ -115,6 +115,7 @@ __host__ __device__ constexpr int prog_layer(int e) {
          : V == 20 ? ANR_L_LBW0 + e
          : V == 21 ? ANR_L_SDF0 + e
          : V == 22 ? ANR_L_LCOL0 + e
+         : V == 23 ? ANR_L_RESD0 + e
          : V == 5 ? ANR_L_SDF0 + e
          : V == 7 ? ANR_L_SREV0 + e
          : V == 6 ? ANR_L_COL0 + e
@@ -447,6 +448,7 @@ static_assert(prog_bias_off<7>(prog_len<7>()) + 256 <= ANR_BIAS_TABLE_FLOATS, "b
 static_assert(prog_bias_off<20>(prog_len<20>()) == seq_bias_off(ANR_L_LBW0, ANR_LBW_LAYERS), "lbw blend-weight bias section");
 static_assert(prog_bias_off<22>(prog_len<22>()) == seq_bias_off(ANR_L_LCOL0, ANR_LCOL_LAYERS), "lbw colour bias section");
 static_assert(prog_bias_off<20>(prog_len<20>()) <= ANR_BIAS_TABLE_FLOATS, "bias table size (anr_layers.h)");
+static_assert(prog_bias_off<23>(prog_len<23>()) == seq_bias_off(ANR_L_RESD0, ANR_RESD_LAYERS), "pdf displacement bias section");
 
 // Fill the bias table once per launch (before the first barrier of the slice stream). Sources:
 // the packed bias section, the novel_pose_bw copy for the pose pass (pose_boff), and the per-frame
@@ -461,7 +463,7 @@ __device__ __forceinline__ void fill_bias_table(const MlpArgs& a, float* __restr
     constexpr int toff = prog_bias_off<V>(e);
     const float* src;
     constexpr int VB = prog_base<V>();
-    if constexpr (VB == 3 || VB == 20) {  // sdf residual MLP / lbw blend-weight MLP: folds of layers 0 / 5
+    if constexpr (VB == 3 || VB == 20 || VB == 23) {  // sdf / pdf residual MLP, lbw blend-weight MLP: folds of layers 0 / 5
       src = e == 0 ? a.fold : e == 5 ? a.fold + 256 : a.bias + toff;
     } else if constexpr (VB == 5 || VB == 7 || VB == 21) {  // sdf network (forward / gradient): the image's bias section
       src = a.bias + toff;
@@ -1871,6 +1873,56 @@ __device__ __forceinline__ void lbw_bw_body(const MlpArgs& a) {
       float* out = a.pbw_rows + row * 24;
       *(f32x4*)(out + 4 * g) = f32x4{v[0] / s, v[1] / s, v[2] / s, v[3] / s};
       if (two) *(f32x4*)(out + 16 + 4 * g) = f32x4{v[4] / s, v[5] / s, v[6] / s, v[7] / s};
+    }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the last (unused) prefetch
+}
+
+// aligned_aninerf_pdf displacement program (V = 23 / 33; anr_pdf_b16.hip / anr_pdf_x6.hip, driven by anr_pdf_capi.hip):
+//   calculate_residual_deformation (aligned_aninerf_pdf_network.py:49-64) per kept sample of one batch, on chip —
+//   the layers of V = 3 / 13 from the same packed sequence (ANR_L_RESD0, poses folded into the layer-0 / layer-5
+//   biases: fold[0..512)), with the epilogue k_sdf_mid applies on the sdf_pdf path done in the lane that holds
+//   resd_fc's three outputs: resd = 0.05 tanh(y) to yr ([n][3], the batch's rows of the compact output; NULL: not
+//   kept) and tpose = x + resd to columns 0..2 of the sample's colour / density input row gb ([n][40]). The density
+//   program reads those columns next: no per-point kernel and no resd_fc row buffer between the two.
+template <bool X6>
+__device__ __forceinline__ void pdf_resd_body(const MlpArgs& a) {
+  constexpr int V = 23 + (X6 ? 10 : 0);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = lane >> 4;
+  const int pl = lane & 15;
+  float* sb = (float*)smem;  // bias table (anr_layers.h LDS layout)
+  fill_bias_table<V>(a, sb, tid);
+  const int n = a.n_rows;
+  const int ntiles = (n + 127) / 128;
+  if ((int)blockIdx.x >= ntiles) return;  // uniform per workgroup, before any LDS-DMA
+
+  Pipe p{smem + mlp_ring_off(), mlp_slice_max<true>(), mlp_nbuf<true>(), a.wimg, 0, wave, lane, 0};
+  p.template start<true, V>();
+
+  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+    const int idx = tile * 128 + wave * 16 + pl;
+    const bool valid = idx < n;
+    const size_t row = (size_t)(valid ? idx : n - 1);
+    const float* pt = a.ptb + row * a.ptb_ld;
+    const float x[3] = {pt[0], pt[1], pt[2]};
+    float emb[16], vemb[8];
+    f32x4 A[17], B[17], fc[2];
+    embed_b<2>(x, g, 10, emb);
+#pragma unroll
+    for (int s8 = 0; s8 < 8; ++s8) vemb[s8] = 0.f;
+    bw_mlp<true, V, 0>(p, emb, vemb, sb, A, B, fc, g, lane);
+    if (valid && g == 0) {
+      float* c = a.gb + row * 40;
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const float rs = 0.05f * tanhf(fc[0][r]);
+        if (a.yr) a.yr[row * 3 + r] = rs;
+        c[r] = x[r] + rs;
+      }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // drain the last (unused) prefetch

@@ -360,6 +360,21 @@ def init_state_dict_lbw(shapes, seed=8642):
     return {n: sd[alias[n]] for n in shapes}
 
 
+def init_state_dict_pdf(shapes, seed=9753):
+    """Deterministic weights for the aligned_aninerf_pdf network (``aligned_aninerf_pdf_network.py``), per tensor
+    a PCG64 stream seeded with (seed, index), by the recipe of ``init_state_dict_sdf``:
+
+      * ``nerf_network.lin*`` and the colour net as ``init_state_dict_lbw`` (density positive on part of the kept
+        samples and zero on the rest);
+      * Conv1d (``resd_linears`` / ``resd_fc``) U(+-1/sqrt(fan_in)), ``resd_fc.weight`` x16, ``resd_fc.bias`` = 0
+        (``aligned_aninerf_pdf_network.py:32``): the displacement 0.05 tanh(.) runs from tanh's linear range (a few
+        mm) to a few cm, short of saturation; embeddings N(0,1).
+    """
+    alias = {n: n.replace('nerf_network', 'sdf_network') for n in shapes}
+    sd = init_state_dict_sdf({alias[n]: s for n, s in shapes.items()}, seed=seed)
+    return {n: sd[alias[n]] for n in shapes}
+
+
 def init_state_dict(shapes, seed=1234, alpha_bias=3.0):
     """Deterministic weights for a state_dict given {name: shape} (insertion order matters).
 

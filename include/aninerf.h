@@ -856,6 +856,104 @@ const uint32_t* anr_lbw_render_knn(const void* workspace, int n_rays, const anr_
 const int32_t* anr_lbw_render_kept(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
 const float* anr_lbw_render_points(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
 
+/* ---- aligned_aninerf_pdf variant (aligned_aninerf_pdf_network.py; the configs/aligned_nerf_pdf yamls) ---
+ * The extended paper's NeRF with a pose-dependent displacement field, eval (no-grad) whole-frame render under
+ * tpose_renderer.render (Network.forward :97-138 per 2048-ray chunk): 5-NN blend over pvertices with the keep mask
+ * pnorm < 0.1 (hard-coded in the network: o->norm_th is NOT read) + the chunk's argmin, LBS pose -> T -> big pose
+ * for points and view directions, the displacement MLP over [gamma_10(init_bigpose), poses] with
+ * resd = 0.05 tanh(.), tpose = init_bigpose + resd, the weight-normed softplus(beta 100) density net,
+ * alpha = 1 - exp(-relu(y0) dist), the IDR colour net without a normal (286 inputs), raw zeroed outside tbounds
+ * widened in place by 0.05 per chunk (strict test on tpose), raw2outputs.
+ * Parameters: the 62 tensors of aligned_aninerf_pdf_network.Network's state_dict, in order:
+ *   0..26  tpose_human.nerf_network.lin{0..8}.{bias, weight_g (o,1), weight_v (o,i)}
+ *          i/o: 39/256, 256/256, 256/256, 256/217, 256/256 x4, 256/257
+ *   27     tpose_human.color_network.color_latent.weight (L,128)
+ *   28..42 tpose_human.color_network.lin{0..4}.{bias, weight_g, weight_v}  i: 286,256,256,384,256
+ *   43     resd_latent.weight (L,128)            (not read by the forward; NULL allowed)
+ *   44..59 resd_linears.{0..7}.{weight,bias}     Conv1d, in: 135,256,256,256,256,391,256,256
+ *   60,61  resd_fc.{weight,bias} (3,256,1)
+ * Precisions: ANR_FP32 (exact fp32 MFMA layer products as layer GEMMs, the parity anchor), ANR_BF16X3 and
+ * ANR_BF16X6 (the displacement MLP with its tanh / tpose epilogue, the density net and the colour net as one
+ * fused launch per batch each, split bf16 with 3 products or, fp32-level, 6).
+ * n_views > 0 applies the novel-view visibility filter of tpose_renderer_mmsk as anr_sdf_frame does: chunks with
+ * no visible sample make no network call and do not widen tbounds.
+ * Not covered (ANR_E_ARG where an option would ask for it): training / autograd, cfg.test_novel_pose,
+ * Network.forward over free samples, N_samples != 64, cfg.tpose_viewdir False, color_with_viewdir False.
+ * The KNN boundary is unpinned as for sdf_pdf: pytorch3d knn_points is restated, not run (k_sdf_front). */
+#define ANR_PDF_NUM_TENSORS 62
+
+typedef struct anr_pdf_params {
+  const float* t[ANR_PDF_NUM_TENSORS];  /* device pointers, state_dict order above */
+} anr_pdf_params;
+
+typedef struct anr_pdf_frame {
+  const float* A;          /* (24,4,4) device */
+  const float* big_A;      /* (24,4,4) device: big pose */
+  const float* R;          /* (3,3) */
+  const float* Th;         /* (3) */
+  const float* pvertices;  /* (V,3) posed SMPL vertices in the pose frame, V <= 6912 */
+  const float* weights;    /* (V,24) skin weights */
+  const float* poses;      /* (72) batch['poses'] */
+  const float* tbounds;    /* (2,3) batch['tbounds'] as passed in */
+  const int64_t* latent_index;  /* (1): colour latent row */
+  int n_verts;
+  /* the visibility filter's views, as anr_sdf_frame's (n_views == 0: off) */
+  int n_views;
+  const float* Ks;         /* (n_views,3,3) */
+  const float* RT;         /* (n_views,3,4) */
+  const uint8_t* msks;     /* (n_views,img_h,img_w) */
+  int img_h, img_w;
+} anr_pdf_frame;
+
+typedef struct anr_pdf_render_out {
+  float* rgb_map;      /* (R,3) */
+  float* acc_map;      /* (R) */
+  float* depth_map;    /* (R) */
+  float* raw;          /* (R*64,4) */
+  float* tbounds_out;  /* (2,3) or NULL: batch['tbounds'] after the in-place widening by 0.05 per chunk (:125-127) */
+} anr_pdf_render_out;
+
+/* Asynchronous on the caller's stream except for one host read of the kept-sample count (it sizes the batches);
+ * allocates nothing. image_only != 0 (cfg.render_image_only): the compact resd rows are not kept; raw and the maps
+ * equal the full call's bit for bit, and anr_pdf_render_rows then has nothing to return.
+ * ANR_E_ARG / ANR_E_WORKSPACE before any HIP call for: a NULL pointer, n_verts outside 1..6912,
+ * o->n_samples != 64, o->novel_pose, a precision other than ANR_FP32 / ANR_BF16X3 / ANR_BF16X6, bad view fields,
+ * a workspace smaller than anr_pdf_render_workspace_bytes(n_rays, o, image_only) (which makes no HIP call; 0 for
+ * bad arguments). Kept samples run in batches of at most 2^18 rows (the environment variable ANR_PDF_BATCH, a
+ * multiple of 256, overrides the batch size for tests; it is read per call and must hold the same value for the
+ * size query and the call). */
+size_t anr_pdf_render_workspace_bytes(int n_rays, const anr_render_opts* o, int image_only);
+int anr_pdf_render_fwd(const anr_pdf_params* p, const anr_pdf_frame* f, const float* ray_o, const float* ray_d,
+                       const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                       const anr_pdf_render_out* out, int image_only, void* workspace, size_t ws_bytes, void* stream);
+/* device int32[2] inside the workspace: {kept samples n', 0}. */
+const int32_t* anr_pdf_render_counts(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+/* copy the resd rows (n',3), in kept order, and / or their sample ids (n'; ray * 64 + sample) out of the workspace
+ * of a full (not image-only) call; NULL outputs are skipped. Reads n' on the host. */
+int anr_pdf_render_rows(const void* workspace, int n_rays, const anr_render_opts* o, float* resd, int32_t* ids,
+                        void* stream);
+/* test views into the workspace of the last call (unstable: they follow the workspace layout, not a contract; for
+ * tests and debugging only): the per-sample KNN records (R*64, 8) as anr_sdf_render_knn, the kept sample ids (n'
+ * int32, in order), the colour-net input rows of the last batch ((rows, 40) floats: tpose in columns 0..2, the
+ * warped view direction in 3..5) and its point rows ((rows, 8): init_bigpose in 0..2, the direction in 3..5,
+ * dist in 6). */
+const uint32_t* anr_pdf_render_knn(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+const int32_t* anr_pdf_render_kept(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+const float* anr_pdf_render_points(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+const float* anr_pdf_render_bigpose(const void* workspace, int n_rays, const anr_render_opts* o, int image_only);
+
+/* Network.get_alpha (:140-174) over n_pts free world points, as aninerf_mesh_renderer's batchify calls it: one
+ * network call per chunk of o->chunk_pts points (a positive multiple of 64; the last chunk partial), each with the
+ * keep mask pnorm < 0.1 (hard-coded; o->norm_th is not read) + the chunk's forced argmin, the displacement MLP and
+ * the density net. alpha (n_pts): the density net's RAW output 0 at kept points (no relu, no 1 - exp, no box test:
+ * get_alpha has none), 0 where a point is dropped. Frame fields read: A, big_A, R, Th, pvertices, weights, poses,
+ * n_verts; n_views must be 0. One host read of the kept count per chunk. ANR_E_ARG before any HIP call for a NULL
+ * pointer, n_pts outside [1, 2^24], a bad chunk_pts, o->novel_pose, another precision, n_verts outside 1..6912;
+ * anr_pdf_alpha_workspace_bytes makes no HIP call and returns 0 for bad arguments. */
+size_t anr_pdf_alpha_workspace_bytes(long n_pts, const anr_alpha_opts* o);
+int anr_pdf_alpha_points(const anr_pdf_params* p, const anr_pdf_frame* f, const float* wpts, long n_pts,
+                         const anr_alpha_opts* o, float* alpha, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- measurement ----------------------------------------------------------------------
  * When enabled, anr_render_fwd records a hipEvent pair around the fused network kernel (k_mlp)
  * on the caller's stream, and anr_sdf_render_fwd one around each fused sdf_pdf network launch. anr_profile_read waits for the recorded events, returns the summed
