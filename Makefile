@@ -19,10 +19,11 @@ DEPS := $(OBJS:.o=.d)
 LIB := animatable_nerf_amd/libaninerf_hip.so
 CXXFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -Iinclude
 
-# test-only entries to the training GEMM launchers (tests/csrc/anr_testapi.hip) and the fused chain programs
-# (tests/csrc/anr_testapi_tchain.hip): the library's own objects plus the hooks, loaded by the kernel tests only
+# test-only entries to the training GEMM launchers (tests/csrc/anr_testapi.hip), the fused chain programs
+# (tests/csrc/anr_testapi_tchain.hip) and the per-sample helpers and small render kernels
+# (tests/csrc/anr_testapi_small.hip): the library's own objects plus the hooks, loaded by the kernel tests only
 TESTLIB := tests/libanr_testapi.so
-TESTOBJ := tests/csrc/anr_testapi.o tests/csrc/anr_testapi_tchain.o
+TESTOBJ := tests/csrc/anr_testapi.o tests/csrc/anr_testapi_tchain.o tests/csrc/anr_testapi_small.o
 DEPS += $(TESTOBJ:.o=.d)
 
 all: $(LIB) $(TESTLIB)

@@ -521,21 +521,29 @@ struct LayerIO {
 #endif
 
 // softplus(beta = 100, threshold = 20) as log2(1 + 2^(100 x log2 e)) ln2 / 100 on the hardware exp2 /
-// log2 (~1 ulp each): 2 transcendentals + 5 VALU instead of the ~25 of k_lgemm's libm-grade epilogue
-// (fast_exp / fast_log1p). Its h feeds a hi/lo bf16 split (~2^-16 relative) and the reverse pass's
-// factor 1 - exp(-100 h); where 1 + e rounds (e < ~1e-3), h and that factor are < 1e-5 and their
-// absolute error < 1e-9. The SDF outputs stay within tests/test_gpu_sdf.py's 1e-4 / 2e-4.
+// log2 (~1 ulp each): 2 transcendentals + 9 VALU (two of them a compare and a select) instead of the
+// ~25 of k_lgemm's libm-grade epilogue (fast_exp / fast_log1p). Its h feeds a hi/lo bf16 split (~2^-16
+// relative) and the reverse pass's factor 1 - exp(-100 h). Where 1 + e rounds (e < 1) the exact
+// rounding error e - ((1 + e) - 1) is added back (log1p(e) = log(u) + err / u, with 1 / u taken as 1: a
+// relative 2^-25 at most; 4 of the 9 VALU): the plain log(1 + e) carries an absolute 6.0e-10 wherever
+// h < 0.0069, 3.9 x 2^-16 relative at h = 1e-5. Measured on the device: |dh| <= 6.4e-12 for h < 1e-5,
+// 0.05 x 2^-16 relative above (tests/test_gpu_math_helpers.py test_softplus100). The SDF outputs stay
+// within tests/test_gpu_sdf.py's 1e-4 / 2e-4.
 __device__ __forceinline__ float softplus100(float x) {
   const float e = __builtin_amdgcn_exp2f(x * 144.269504f);
-  const float h = __builtin_amdgcn_logf(1.0f + e) * 0.00693147181f;
+  const float u = 1.0f + e;
+  const float err = e < 1.0f ? e - (u - 1.0f) : 0.0f;  // the exact rounding error of 1 + e (u - 1 is exact below 2)
+  const float h = __builtin_fmaf(err, 0.01f, __builtin_amdgcn_logf(u) * 0.00693147181f);
   return x * 100.f > 20.f ? x : h;
 }
 
 // the fp32-level programs (V >= 10): torch's softplus(beta = 100, threshold = 20) = log1p(exp(100 x)) /
 // 100 and its backward factor sigmoid(100 x) = e / (1 + e) (torch's softplus_backward: z / (z + 1),
-// z = exp(100 x)) from ONE exp and ONE log, both within ~2 ulp of fp64 over the whole range (numpy
-// emulation with correctly rounded exp2 / log2: <= 4.3 units of 2^-24 relative; torch's own fp32
-// evaluation is off by up to 65 there, its RN(100 x) amplified by the exp):
+// z = exp(100 x)) from ONE exp and ONE log (numpy emulation with correctly rounded exp2 / log2:
+// <= 4.3 units of 2^-24 relative; torch's own fp32 evaluation is off by up to 65 there, its RN(100 x)
+// amplified by the exp). Measured on the device against float64 over -1.2 <= x <= 0.5, subnormal
+// results included: DESIGN.md "Helper accuracy, measured on the device",
+// tests/test_gpu_math_helpers.py test_softplus100_fac_*.
 //   e = 2^(x C) with C = 100 log2(e) as C_hi + C_lo and the residual of x C_hi exact by FMA, so the
 //       hardware exp2 sees the argument to ~2^-48 and e = 2^a (1 + a_lo ln2);
 //   log1p(e) = log(u) + (e - (u - 1)) / u with u = RN(1 + e): e - (u - 1) is the exact rounding error
@@ -543,18 +551,22 @@ __device__ __forceinline__ float softplus100(float x) {
 // Above torch's threshold (100 x > 20) softplus returns x and passes the gradient: here the argument
 // is clamped to 0.4 (no overflow: e <= e^40) and h = max(h, x), which is x wherever log1p(exp(-100 x))
 // / 100 < x's half ulp (from 100 x ~ 17 on, within ~1 ulp of torch's x between 20 and 40), and the
-// factor e / (1 + e) is 1 within an ulp there. No compare masks: 15 VALU + 3 transcendentals for the
-// pair, against ~27 + 3 for the libm-grade fast_exp / fast_log1p softplus alone and ~15 + 1 more for
+// factor e / (1 + e) is 1 within an ulp there. One compare mask, for the subnormal results (a compare,
+// two selects, an add and a multiply): 20 VALU + 3 transcendentals for the pair, against ~27 + 3 for the libm-grade fast_exp / fast_log1p softplus alone and ~15 + 1 more for
 // the factor recomputed from h (1 - exp(-100 h), with a series) in the reverse pass: the bf16x6 SDF
 // forward stores the factor itself, its input gradient multiplies.
 __device__ __forceinline__ float softplus100_fac(float x, float& fac) {
+#pragma clang fp contract(off)  // a must stay RN(xc C_HI), the value a_lo is the residual of, where 64 is added to it
   constexpr float C_HI = 144.26950073242188f, C_LO = 3.356474508109386e-06f;
   constexpr float LN2 = 0.6931471824645996f;
   const float xc = fminf(x, 0.4f);
   const float a = xc * C_HI;
   const float a_lo = __builtin_fmaf(xc, C_LO, __builtin_fmaf(xc, C_HI, -a));
-  const float E = __builtin_amdgcn_exp2f(a);
-  const float e = __builtin_fmaf(E, a_lo * LN2, E);
+  // v_exp_f32 flushes subnormal results: below 2^-100 the exponent is raised by 64 (a + 64 is exact) and e scaled
+  // back, so that e, and with it h = e / 100 and fac = e, round once into the subnormal range as torch's do
+  const bool tiny = a < -100.f;
+  const float E = __builtin_amdgcn_exp2f(a + (tiny ? 64.f : 0.f));
+  const float e = __builtin_fmaf(E, a_lo * LN2, E) * (tiny ? 0x1p-64f : 1.f);
   const float u = 1.f + e;
   const float err = e - (u - 1.f);
   const float ru = __builtin_amdgcn_rcpf(u);
@@ -1076,8 +1088,11 @@ __device__ __forceinline__ void layer(Pipe& p, const f32x4 (&in)[NIN], const flo
 }
 
 // sin and cos of x sharing one Cody-Waite reduction (three-constant FMA split of pi/2, accurate for
-// |x| <= 1e5) and cephes' minimax polynomials on [-pi/4, pi/4]: <= 1.5 ulp, 7e-8 absolute (checked
-// against float64 over |x| <= 5e4). Branch-free; embed_b keeps larger arguments on the library path.
+// |x| <= 1e5) and cephes' minimax polynomials on [-pi/4, pi/4]: <= 1.53 ulp, 7.2e-8 absolute, measured
+// on the device against float64 over every float of 32768 <= |x| <= 65536 (embed_b sends arguments up
+// to 65536 here), every 37th below and the floats around k pi / 2: sin 1.526 ulp / 7.09e-8, cos 1.521
+// ulp / 7.11e-8 (tests/test_gpu_math_helpers.py). sin(-0.0) is +0.0. Branch-free; embed_b keeps larger
+// arguments on the library path.
 __device__ __forceinline__ void sincos_fast(float x, float& s, float& c) {
   const float k = __builtin_rintf(x * 0.636619772367581343f);
   float r = __builtin_fmaf(-k, 1.57079601287841796875f, x);      // 0x1.921fb0p+0

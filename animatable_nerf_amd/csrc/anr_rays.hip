@@ -561,8 +561,10 @@ __global__ __launch_bounds__(1024) void k_compact1(CompactArgs a, int* __restric
 // ------------------------------------------------------------------------------------------
 // alpha_ind (tpose_nerf_network.py:186-196): sigma' > train_th, plus per-chunk argmax(sigma')
 // ------------------------------------------------------------------------------------------
+// -0.0 orders as +0.0: torch.argmax compares values, so among signed zeros at a chunk's maximum the first wins
 __device__ __forceinline__ uint32_t ordered_bits(float v) {
-  const uint32_t u = __float_as_uint(v);
+  const uint32_t u0 = __float_as_uint(v);
+  const uint32_t u = u0 == 0x80000000u ? 0u : u0;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
