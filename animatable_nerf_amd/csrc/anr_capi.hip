@@ -29,11 +29,6 @@ int check_launch(const char* what) {
   return ANR_OK;
 }
 
-}  // namespace anr
-
-namespace {
-
-
 int num_cus() {
   static int cached[64] = {0};
   int dev = 0;
@@ -45,6 +40,10 @@ int num_cus() {
   }
   return cached[dev];
 }
+
+}  // namespace anr
+
+namespace {
 
 bool mlp_attr_set = false;
 bool mlp_img_attr_set = false;

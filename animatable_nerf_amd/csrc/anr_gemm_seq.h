@@ -1,6 +1,8 @@
-// anr_gemm_seq.h — host side of the layer-wise GEMM sequences of the sdf_pdf and aligned_aninerf_lbw renders
-// (anr_sdf_capi.hip, anr_lbw_capi.hip): the per-call cache of split-bf16 weight images and the launcher that
-// routes one layer to k_lgemm (anr_lgemm.hip) or k_gemm (anr_gemm.hip). Host code only.
+// anr_gemm_seq.h — host side of the layer-wise GEMM sequences of the sdf_pdf, aligned_aninerf_lbw and
+// aligned_aninerf_pdf renders (anr_sdf_capi.hip, anr_lbw_capi.hip, anr_pdf_capi.hip): the per-call cache of
+// split-bf16 weight images, the launcher that routes one layer to k_lgemm (anr_lgemm.hip) or k_gemm (anr_gemm.hip),
+// and the layer sequences those renders share (G::skip8, density_sp, colour5). The front-end, compaction and
+// fused-image stage they share is anr_knn_host.h. Host code only.
 #pragma once
 #include <cstdlib>
 
@@ -148,6 +150,54 @@ struct G {
     g.spd = spd; g.ldsd = 256; g.spd_n = spd_n; g.spd_h = spd ? spd_h : 0; g.spd_scale = spd_scale;
     g.div_pre = div_pre;
     return run(g);
+  }
+
+  // ---- whole layer sequences over the scratch activations Ha / Hb ([M][256] each)
+  // The 8-layer-plus-fc skip MLP (sdf_pdf / aligned_aninerf_pdf resd, aligned_aninerf_lbw bw) over X = gamma_10
+  // ([M][64], K_in columns) -> Y[:, :nY]. W[l] / B[l]: layer l's weight / bias; layers 0 and 5 (in_ch0 / in_ch5
+  // weight columns, layer 5 = [X | h4]) take the folded biases fold0 / fold5 (the latent or pose columns folded
+  // in). try_head: layer 7 + fc as one k_lgemm HEAD launch where that runs.
+  int skip8(float* Y, long ldY, int nY, const float* const W[8], const float* const B[8], const float* fcW,
+            const float* fcB, const float* fold0, const float* fold5, const float* X, int K_in, int in_ch0, int in_ch5,
+            float* Ha, float* Hb, bool try_head) {
+    ANR_TRY(fwd(Ha, 256, 256, W[0], in_ch0, fold0, X, 64, K_in, 0, true));
+    ANR_TRY(fwd(Hb, 256, 256, W[1], 256, B[1], Ha, 256, 256, 0, true));
+    ANR_TRY(fwd(Ha, 256, 256, W[2], 256, B[2], Hb, 256, 256, 0, true));
+    ANR_TRY(fwd(Hb, 256, 256, W[3], 256, B[3], Ha, 256, 256, 0, true));
+    ANR_TRY(fwd(Ha, 256, 256, W[4], 256, B[4], Hb, 256, 256, 0, true));
+    ANR_TRY(fwd(Hb, 256, 256, W[5], in_ch5, fold5, X, 64, K_in, 0, true, nullptr, 0.f, false, Ha, 256, 256, in_ch0));
+    ANR_TRY(fwd(Ha, 256, 256, W[6], 256, B[6], Hb, 256, 256, 0, true));
+    if (try_head && fwd_head(Y, ldY, nY, fcW, fcB, W[7], 256, B[7], Ha, 256, 256))
+      return check_launch("k_lgemm (skip MLP, layer 7 + fc)");
+    ANR_TRY(fwd(Hb, 256, 256, W[7], 256, B[7], Ha, 256, 256, 0, true));
+    return fwd(Y, ldY, nY, fcW, 256, fcB, Hb, 256, 256, 0, false);
+  }
+  // The density net of aligned_aninerf_lbw / _pdf: weight-normed layers WN[0..8] (biases tp[3 l]) over Xs0
+  // ([M][40], gamma_6) -> Y8 ([M][264]: density, feature). Softplus outputs only, no stored factors (nothing
+  // differentiates here: the dummy factor pointer selects the softplus epilogue of lin3); lin3 writes X4 (217
+  // outputs / sqrt2 beside the gamma columns the caller put there), which lin4 reads.
+  int density_sp(const float* const* WN, const float* const* tp, const float* Xs0, float* X4, float* Y8, float* Ha,
+                 float* Hb) {
+    ANR_TRY(fwd_sp(Ha, WN[0], 39, tp[0], Xs0, 40, nullptr));
+    ANR_TRY(fwd_sp(Hb, WN[1], 256, tp[3], Ha, 256, nullptr));
+    ANR_TRY(fwd_sp(Ha, WN[2], 256, tp[6], Hb, 256, nullptr));
+    ANR_TRY(fwd(X4, 256, 217, WN[3], 256, tp[9], Ha, 256, 256, 0, false, Hb, 1.41421356237309515f, true));
+    ANR_TRY(fwd_sp(Ha, WN[4], 256, tp[12], X4, 256, nullptr));
+    ANR_TRY(fwd_sp(Hb, WN[5], 256, tp[15], Ha, 256, nullptr));
+    ANR_TRY(fwd_sp(Ha, WN[6], 256, tp[18], Hb, 256, nullptr));
+    ANR_TRY(fwd_sp(Hb, WN[7], 256, tp[21], Ha, 256, nullptr));
+    return fwd(Y8, 264, 257, WN[8], 256, tp[24], Hb, 256, 256, 0, false);
+  }
+  // The colour net of aligned_aninerf_lbw / _pdf: WN[9..13] (biases tp[cb + 3 l]) over [tpose, gamma_4(tpose_dir)]
+  // (30 columns of C0, [M][40]) || feature (Y8 columns 1..256) -> Yc ([M][4]); fold3: lin3's bias with
+  // color_latent folded in
+  int colour5(const float* const* WN, const float* const* tp, int cb, const float* fold3, const float* C0,
+              const float* Y8, float* Yc, float* Ha, float* Hb) {
+    ANR_TRY(fwd(Ha, 256, 256, WN[9], 286, tp[cb], C0, 40, 30, 0, true, nullptr, 0.f, false, Y8 + 1, 264, 256, 30));
+    ANR_TRY(fwd(Hb, 256, 256, WN[10], 256, tp[cb + 3], Ha, 256, 256, 0, true));
+    ANR_TRY(fwd(Ha, 256, 256, WN[11], 256, tp[cb + 6], Hb, 256, 256, 0, true));
+    ANR_TRY(fwd(Hb, 256, 256, WN[12], 384, fold3, Ha, 256, 256, 0, true));
+    return fwd(Yc, 4, 3, WN[13], 256, tp[cb + 12], Hb, 256, 256, 0, false);
   }
 };
 

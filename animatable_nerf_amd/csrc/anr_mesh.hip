@@ -157,14 +157,6 @@ AlphaLayout alpha_layout(long n_pts, int chunk_pts, long np) {
 
 bool alpha_attr_set = false;
 
-int num_cus_here() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
-    return 256;
-  return v;
-}
-
 struct McLayout {
   size_t flags, cases, voff, toff, vblock, tblock, counts, total;
 };
@@ -309,7 +301,7 @@ int anr_alpha_points(const anr_params* p, const anr_frame* f, const float* wpts,
     alpha_attr_set = true;
   }
   const long max_tiles = ((long)G * 64 + 127) / 128;
-  const int cus = num_cus_here();
+  const int cus = num_cus();
   const int grid = (int)(max_tiles < cus ? max_tiles : cus);
   if (x6) hipLaunchKernelGGL(k_alpha_x6, dim3(grid), dim3(512), mlp_lds_bytes<true>(), s, ma);
   else if (b16) hipLaunchKernelGGL(k_alpha_b16, dim3(grid), dim3(512), mlp_lds_bytes<true>(), s, ma);

@@ -11,6 +11,8 @@
 //   -> compositing (k_composite) -> msk_sdf lists.
 // Layer-wise GEMMs (anr_gemm.hip exact fp32 MFMA, or anr_lgemm.hip split-bf16) keep each activation in HBM: the input gradient
 // needs every softplus factor of the forward, which does not fit a fused register pipeline.
+// The front-end + compaction stage, the free-point search of anr_knn_blend and the image packing are the KNN family's
+// shared host code (anr_knn_host.h); the residual MLP's fp32 sequence is G::skip8 (anr_gemm_seq.h).
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -19,6 +21,7 @@
 #include "anr_common.h"
 #include "anr_gemm_seq.h"
 #include "anr_kernels.h"
+#include "anr_knn_host.h"
 #include "anr_sdf.h"
 #include "anr_train.h"
 #include "anr_ws.h"
@@ -34,7 +37,8 @@ constexpr long SDF_BATCH = 1L << ANR_SDF_BATCH_LOG2;  // kept samples per layer-
 constexpr size_t SDF_LIMG_BYTES = 16u << 20;  // split-bf16 layer-GEMM weight images (31 GEMMs, <= 384 KiB each)
 
 struct SLayout {
-  size_t counts, mask, chunk_min, ray_off, block_sum, list, knn, tbtab, wimg, fold, limg, rimg, simg, gimg, cimg, resd_rows, grad_rows;
+  KnnFrontLayout F;
+  size_t wimg, fold, limg, rimg, simg, gimg, cimg, resd_rows, grad_rows;
   size_t min_sdf, flags, chunk_cnt, msk_sdf, msk_label;
   size_t ptb, Gr, Ha, Hb, Yr, Xs0, X4, D, Y8, Ga, Gb, Gc, gB, C0, Yc;
   long P;
@@ -46,23 +50,14 @@ SLayout slayout(int n_rays, int chunk) {
   const size_t R = (size_t)n_rays, N = R * 64;
   const size_t nch = (R + chunk - 1) / (size_t)std::max(chunk, 1);
   Carve c;
-  L.counts = c.bytes(16);
-  L.mask = c.bytes(R * 8);
-  L.chunk_min = c.bytes(nch * 8);
-  L.ray_off = c.bytes((R + 1) * 4);
-  L.block_sum = c.bytes(((R + 255) / 256) * 4);
-  L.list = c.bytes(N * 4);
-  L.knn = c.bytes(N * 32);
-  L.tbtab = c.bytes(nch * 6 * 4);
+  L.F.carve(c, R, chunk);
   L.wimg = c.bytes(SDF_WN_FLOATS * 4);
   L.fold = c.bytes(768 * 4);
   L.limg = c.bytes(SDF_LIMG_BYTES);
-  // the fused programs' images: bf16x3 (k_pack_seq) or bf16x6 (k_pack_seq_x6), sized for the larger
-  auto img = [&](int L0, int nl) { return c.bytes((size_t)std::max(seq_image_bytes(L0, nl), x6seq_image_bytes(L0, nl))); };
-  L.rimg = img(ANR_L_RESD0, ANR_RESD_LAYERS);
-  L.simg = img(ANR_L_SDF0, ANR_SDF_LAYERS);
-  L.gimg = img(ANR_L_SREV0, ANR_SREV_LAYERS);
-  L.cimg = img(ANR_L_COL0, ANR_COL_LAYERS);
+  L.rimg = carve_seq_image(c, ANR_L_RESD0, ANR_RESD_LAYERS);
+  L.simg = carve_seq_image(c, ANR_L_SDF0, ANR_SDF_LAYERS);
+  L.gimg = carve_seq_image(c, ANR_L_SREV0, ANR_SREV_LAYERS);
+  L.cimg = carve_seq_image(c, ANR_L_COL0, ANR_COL_LAYERS);
   L.resd_rows = c.bytes(N * 3 * 4);
   L.grad_rows = c.bytes(N * 3 * 4);
   L.min_sdf = c.bytes(R * 4);
@@ -80,31 +75,18 @@ SLayout slayout(int n_rays, int chunk) {
   return L;
 }
 
-int sdf_cus() {
-  int dev = 0, v = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) return 256;
-  return v;
-}
-
 int check(const anr_sdf_params* p, const anr_sdf_frame* f, const float* ray_o, const float* ray_d, const float* near_,
           const float* far_, int R, const anr_render_opts* o, const anr_sdf_render_out* out, void* ws) {
-  if (!p || !f || !o || !out || !ws || !ray_o || !ray_d || !near_ || !far_)
-    return fail(ANR_E_ARG, "sdf render: NULL argument");
-  if (o->n_samples != 64) return fail(ANR_E_ARG, "sdf render: only N_samples == 64 is supported");
-  if (o->chunk <= 0 || R <= 0) return fail(ANR_E_ARG, "sdf render: bad chunk / n_rays");
-  if (o->novel_pose) return fail(ANR_E_ARG, "sdf render: novel_pose is an aninerf option");
+  ANR_TRY(check_knn_common("sdf render", p && f && out, ray_o, ray_d, near_, far_, R, o, ws, 0,
+                           "novel_pose is an aninerf option", false));
   for (int i = 0; i < ANR_SDF_NUM_TENSORS; ++i)
     if (!p->t[i] && i != SDF_RESD_LAT) return fail(ANR_E_ARG, "sdf render: NULL parameter tensor");
   if (!f->A || !f->big_A || !f->R || !f->Th || !f->poses || !f->pvertices || !f->weights || !f->tbounds ||
       !f->latent_index || !f->occupancy)
     return fail(ANR_E_ARG, "sdf render: NULL frame tensor");
-  if (f->n_verts <= 0 || f->n_verts > 6912) return fail(ANR_E_ARG, "sdf render: n_verts must be in [1, 6912]");
-  if (!out->rgb_map || !out->acc_map || !out->depth_map || !out->raw || !out->sdf)
-    return fail(ANR_E_ARG, "sdf render: NULL output");
-  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
-    return fail(ANR_E_ARG, "sdf render: bad visibility-filter views");
-  return ANR_OK;
+  return check_knn_frame("sdf render", f->n_verts,
+                         out->rgb_map && out->acc_map && out->depth_map && out->raw && out->sdf, f->n_views, f->Ks,
+                         f->RT, f->msks, f->img_h, f->img_w);
 }
 
 }  // namespace
@@ -118,12 +100,12 @@ size_t anr_sdf_render_workspace_bytes(int n_rays, const anr_render_opts* o) {
 
 const int32_t* anr_sdf_render_counts(const void* workspace, int n_rays, const anr_render_opts* o) {
   if (!workspace || !o || o->chunk <= 0) return nullptr;
-  return (const int32_t*)((const char*)workspace + slayout(n_rays, o->chunk).counts);
+  return (const int32_t*)((const char*)workspace + slayout(n_rays, o->chunk).F.counts);
 }
 
 const uint32_t* anr_sdf_render_knn(const void* workspace, int n_rays, const anr_render_opts* o) {
   if (!workspace || !o || o->chunk <= 0 || n_rays <= 0) return nullptr;
-  return (const uint32_t*)((const char*)workspace + slayout(n_rays, o->chunk).knn);
+  return (const uint32_t*)((const char*)workspace + slayout(n_rays, o->chunk).F.knn);
 }
 
 int anr_sdf_render_rows(const void* workspace, int n_rays, const anr_render_opts* o, float* resd, float* gradients,
@@ -133,7 +115,7 @@ int anr_sdf_render_rows(const void* workspace, int n_rays, const anr_render_opts
   const char* ws = (const char*)workspace;
   int cnt[2];
   hipStream_t s = (hipStream_t)stream;
-  if (hipMemcpyAsync(cnt, ws + L.counts, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+  if (hipMemcpyAsync(cnt, ws + L.F.counts, 8, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     return fail(ANR_E_HIP, "anr_sdf_render_rows: count readback");
   auto cp = [&](void* dst, size_t off, size_t bytes) {
     if (!dst || bytes == 0) return hipSuccess;
@@ -160,18 +142,14 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
   if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "sdf render: workspace too small");
   char* ws = (char*)workspace;
   const int nch = (R + chunk - 1) / chunk;
-  int* counts = (int*)(ws + L.counts);
+  int* counts = (int*)(ws + L.F.counts);
   float4* raw = (float4*)out->raw;
 
-  if (hipMemsetAsync(ws + L.counts, 0, 16, s) != hipSuccess ||
-      hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess)
-    return fail(ANR_E_HIP, "sdf render: memset");
-
-  // per-call weight preparation (weight norm, folds, per-chunk tbounds)
+  // per-call weight preparation (weight norm, folds; the per-chunk tbounds: knn_front_compact)
   const float* const* tp = p->t;
   float* wimg = (float*)(ws + L.wimg);
   float* fold = (float*)(ws + L.fold);
-  float* tbtab = (float*)(ws + L.tbtab);
+  float* tbtab = (float*)(ws + L.F.tbtab);
   SdfTensors T{};
   for (int i = 0; i < ANR_SDF_NUM_TENSORS; ++i) T.t[i] = tp[i];
   hipLaunchKernelGGL(k_sdf_wnorm, dim3(sdf_wn_rows()), dim3(256), 0, s, T, wimg);
@@ -179,40 +157,19 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
   hipLaunchKernelGGL(k_sdf_fold, dim3(3), dim3(256), 0, s, T, (const float*)wimg, f->poses, f->latent_index, fold);
   ANR_TRY(check_launch("k_sdf_fold"));
   const bool filt = !wpts && f->n_views > 0;  // visibility filter: widening depends on the front-end
-  if (!filt) {
-    hipLaunchKernelGGL(k_sdf_tbtab, dim3(1), dim3(64), 0, s, f->tbounds, nch, tbtab, out->tbounds_out, nullptr);
-    ANR_TRY(check_launch("k_sdf_tbtab"));
-  }
 
   // B1 front-end + ordered compaction
   SdfFrontArgs fa{};
   fa.ray_o = ray_o; fa.ray_d = ray_d; fa.near_ = near_; fa.far_ = far_; fa.t_rand = o->t_rand;
   fa.wpts = wpts; fa.n_pts = n_pts;
   fa.n_rays = R; fa.chunk = chunk; fa.R = f->R; fa.Th = f->Th; fa.verts = f->pvertices; fa.nv = f->n_verts;
-  fa.norm_th = o->norm_th; fa.mask = (uint64_t*)(ws + L.mask); fa.chunk_min = (uint64_t*)(ws + L.chunk_min);
-  fa.knn = (uint32_t*)(ws + L.knn); fa.raw = raw; fa.sdf = out->sdf;
-  const int grid_front = std::min(sdf_cus(), (R + 15) / 16);
+  fa.norm_th = o->norm_th; fa.raw = raw; fa.sdf = out->sdf;
   if (filt) {
     fa.n_views = f->n_views; fa.Ks = f->Ks; fa.RT = f->RT; fa.msks = f->msks; fa.img_h = f->img_h; fa.img_w = f->img_w;
   }
-  hipLaunchKernelGGL(k_sdf_front, dim3(grid_front), dim3(1024), 0, s, fa);
-  ANR_TRY(check_launch("k_sdf_front"));
-  if (filt) {
-    hipLaunchKernelGGL(k_sdf_tbtab, dim3(1), dim3(64), 0, s, f->tbounds, nch, tbtab, out->tbounds_out,
-                       (const uint64_t*)fa.chunk_min);
-    ANR_TRY(check_launch("k_sdf_tbtab (visible chunks)"));
-  }
-  CompactArgs ca{};
-  ca.n_rays = R; ca.chunk = chunk; ca.mask = fa.mask; ca.chunk_min = fa.chunk_min;
-  ca.ray_off = (int*)(ws + L.ray_off); ca.block_sum = (int*)(ws + L.block_sum); ca.list = (int*)(ws + L.list);
-  const int nb = (R + 255) / 256;
-  hipLaunchKernelGGL(k_count, dim3(nb), dim3(256), 0, s, ca);
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, ca.block_sum, nb, counts);
-  hipLaunchKernelGGL(k_compact, dim3((R + 3) / 4), dim3(256), 0, s, ca);
-  ANR_TRY(check_launch("k_compact (sdf)"));
   int n = 0;
-  if (hipMemcpyAsync(&n, counts, 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return fail(ANR_E_HIP, "sdf render: kept-count readback");
+  ANR_TRY(knn_front_compact(fa, ws, L.F, f->tbounds, out->tbounds_out, filt, "sdf render", s, &n));
+  const int* list = (const int*)(ws + L.F.list);
 
   // per batch of kept samples
   float beta = 0.f;
@@ -222,61 +179,36 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
   float *Ha = F(L.Ha), *Hb = F(L.Hb), *Ga = F(L.Ga), *Gb = F(L.Gb), *Gc = F(L.Gc), *D = F(L.D);
   const long P = L.P;
   auto Dl = [&](int l) { return D + (size_t)l * P * 256; };
-  auto WN = [&](int l) { return (const float*)wimg + wn_layer(l).off; };
+  const float* WN[SDF_NUM_WN];
+  for (int l = 0; l < SDF_NUM_WN; ++l) WN[l] = wimg + wn_layer(l).off;
   const float sqrt2 = 1.41421356237309515f;
   LImgCache limg;
   limg.base = ws + L.limg;
   limg.cap = SDF_LIMG_BYTES;
-  const int cus = sdf_cus();
+  const int cus = num_cus();
   // split-bf16: the residual MLP, the SDF network forward, its input gradient and the colour net as
   // one fused launch per batch each (anr_resd_b16.hip), their weight images packed once per call;
   // ANR_BF16X6: the same four fused launches as fp32-level bf16x6 programs (anr_resd_x6.hip)
   const bool x6 = o->precision == ANR_BF16X6;
   const bool fused = x6 || o->precision == ANR_BF16X3;
-  // the bf16x6 images' weight bytes (the bias section follows them)
-  auto wbytes = [&](int L0, int nl) { return x6 ? x6seq_wbytes(L0, nl) : seq_wbytes(L0, nl); };
-  auto pack = [&](const PackArgs& pa, int L0, int nl, int sl, float sc) {
-    const int nt = x6 ? seq_x6_pack_threads(L0, nl) : seq_pack_threads(L0, nl);
-    if (x6) hipLaunchKernelGGL(k_pack_seq_x6, dim3((nt + 255) / 256), dim3(256), 0, s, pa, L0, nl, sl, sc);
-    else hipLaunchKernelGGL(k_pack_seq, dim3((nt + 255) / 256), dim3(256), 0, s, pa, L0, nl, sl, sc);
-    return check_launch(x6 ? "k_pack_seq_x6" : "k_pack_seq");
-  };
+  const SeqImages im{s, x6, "sdf"};
   unsigned char* rimg = (unsigned char*)(ws + L.rimg);
   unsigned char* simg = (unsigned char*)(ws + L.simg);
   unsigned char* gimg = (unsigned char*)(ws + L.gimg);
   unsigned char* cimg = (unsigned char*)(ws + L.cimg);
-  if (fused) {
-    PackArgs pa{};
-    for (int l = 0; l < 8; ++l) {
-      pa.t[l] = tp[SDF_RLIN0 + 2 * l];
-      pa.t[9 + l] = l == 0 || l == 5 ? nullptr : tp[SDF_RLIN0 + 2 * l + 1];  // folded with the poses
-    }
-    pa.t[8] = tp[SDF_RFC_W];
-    pa.t[17] = tp[SDF_RFC_B];
-    pa.out = rimg;
-    ANR_TRY(pack(pa, ANR_L_RESD0, ANR_RESD_LAYERS, -1, 1.0f));
-    PackArgs ps{};
-    for (int l = 0; l < 9; ++l) {
-      ps.t[l] = WN(l);
-      ps.t[9 + l] = tp[3 * l];
-    }
-    ps.out = simg;
-    ANR_TRY(pack(ps, ANR_L_SDF0, ANR_SDF_LAYERS, 4, 1.0f / sqrt2));
-    for (int l = 9; l < 18; ++l) ps.t[l] = nullptr;  // no biases in the gradient pass
-    ps.out = gimg;  // lin7 .. lin0 transposed, lin4's with the skip's 1/sqrt2 (entry 3)
-    ANR_TRY(pack(ps, ANR_L_SREV0, ANR_SREV_LAYERS, 3, 1.0f / sqrt2));
-    PackArgs pc{};
-    for (int l = 0; l < 5; ++l) {
-      pc.t[l] = WN(9 + l);
-      pc.t[9 + l] = l == 3 ? nullptr : tp[SDF_CLIN0 + 3 * l];  // lin3's bias: the latent fold
-    }
-    pc.out = cimg;
-    ANR_TRY(pack(pc, ANR_L_COL0, ANR_COL_LAYERS, -1, 1.0f));
+  if (fused) {  // the residual MLP's layer 0 / 5 biases: folded with the poses
+    ANR_TRY(im.pack_skip8(tp, SDF_RLIN0, SDF_RFC_W, SDF_RFC_B, ANR_L_RESD0, ANR_RESD_LAYERS, rimg));
+    ANR_TRY(im.pack_density(WN, tp, simg));
+    PackArgs pr{};  // the gradient pass: lin7 .. lin0 transposed, no biases, lin4's with the skip's 1/sqrt2 (entry 3)
+    for (int l = 0; l < 9; ++l) pr.t[l] = WN[l];
+    pr.out = gimg;
+    ANR_TRY(im.pack(pr, ANR_L_SREV0, ANR_SREV_LAYERS, 3, 1.0f / sqrt2));
+    ANR_TRY(im.pack_colour(WN, tp, SDF_CLIN0, ANR_L_COL0, ANR_COL_LAYERS, cimg));
   }
   for (long b0 = 0; b0 < n; b0 += P) {
     const int cnt = (int)std::min<long>(P, n - b0);
     SdfPointArgs a{};
-    a.list = ca.list; a.b0 = (int)b0; a.cnt = cnt;
+    a.list = list; a.b0 = (int)b0; a.cnt = cnt;
     a.ray_o = ray_o; a.ray_d = ray_d; a.near_ = near_; a.far_ = far_; a.t_rand = o->t_rand; a.chunk = chunk;
     a.wpts = wpts; a.vdir = vdir; a.n_pts = n_pts;
     a.R = f->R; a.Th = f->Th; a.A = f->A; a.bigA = f->big_A; a.weights = f->weights; a.knn = fa.knn;
@@ -292,8 +224,7 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
     ANR_TRY(check_launch("k_sdf_prep"));
     if (fused) {
       MlpArgs ra{};
-      ra.wimg = rimg;
-      ra.bias = (const float*)(rimg + wbytes(ANR_L_RESD0, ANR_RESD_LAYERS));
+      im.bind(ra, rimg, ANR_L_RESD0, ANR_RESD_LAYERS);
       ra.fold = fold;
       ra.ptb = a.ptb;
       ra.ptb_ld = 8;
@@ -301,21 +232,13 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
       ra.n_rows = cnt;
       if (launch_resd(ra, cus, s, x6) != 0) return fail(ANR_E_HIP, "k_resd launch failed");
     } else {
-    const float* Wr[8];
-    for (int l = 0; l < 8; ++l) Wr[l] = tp[SDF_RLIN0 + 2 * l];
-    ANR_TRY(g.fwd(Ha, 256, 256, Wr[0], 135, fold, a.Gr, 64, 63, 0, true));
-    ANR_TRY(g.fwd(Hb, 256, 256, Wr[1], 256, tp[SDF_RLIN0 + 3], Ha, 256, 256, 0, true));
-    ANR_TRY(g.fwd(Ha, 256, 256, Wr[2], 256, tp[SDF_RLIN0 + 5], Hb, 256, 256, 0, true));
-    ANR_TRY(g.fwd(Hb, 256, 256, Wr[3], 256, tp[SDF_RLIN0 + 7], Ha, 256, 256, 0, true));
-    ANR_TRY(g.fwd(Ha, 256, 256, Wr[4], 256, tp[SDF_RLIN0 + 9], Hb, 256, 256, 0, true));
-    ANR_TRY(g.fwd(Hb, 256, 256, Wr[5], 391, fold + 256, a.Gr, 64, 63, 0, true, nullptr, 0.f, false, Ha, 256, 256, 135));
-    ANR_TRY(g.fwd(Ha, 256, 256, Wr[6], 256, tp[SDF_RLIN0 + 13], Hb, 256, 256, 0, true));
-    if (g.fwd_head(F(L.Yr), 4, 3, tp[SDF_RFC_W], tp[SDF_RFC_B], Wr[7], 256, tp[SDF_RLIN0 + 15], Ha, 256, 256)) {
-      ANR_TRY(check_launch("k_lgemm (sdf, resd_linears.7 + resd_fc)"));
-    } else {
-      ANR_TRY(g.fwd(Hb, 256, 256, Wr[7], 256, tp[SDF_RLIN0 + 15], Ha, 256, 256, 0, true));
-      ANR_TRY(g.fwd(F(L.Yr), 4, 3, tp[SDF_RFC_W], 256, tp[SDF_RFC_B], Hb, 256, 256, 0, false));
-    }
+      const float *Wr[8], *Br[8];
+      for (int l = 0; l < 8; ++l) {
+        Wr[l] = tp[SDF_RLIN0 + 2 * l];
+        Br[l] = tp[SDF_RLIN0 + 2 * l + 1];
+      }
+      ANR_TRY(g.skip8(F(L.Yr), 4, 3, Wr, Br, tp[SDF_RFC_W], tp[SDF_RFC_B], fold, fold + 256, a.Gr, 63, 135, 391, Ha, Hb,
+                      true));
     }
     hipLaunchKernelGGL(k_sdf_mid, pg, pb, 0, s, a);
     ANR_TRY(check_launch("k_sdf_mid"));
@@ -329,8 +252,7 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
     const float* hin = nullptr;
     if (fused) {
       MlpArgs sa{};
-      sa.wimg = simg;
-      sa.bias = (const float*)(simg + wbytes(ANR_L_SDF0, ANR_SDF_LAYERS));
+      im.bind(sa, simg, ANR_L_SDF0, ANR_SDF_LAYERS);
       sa.ptb = a.C0;
       sa.ptb_ld = 40;
       for (int l = 0; l < 8; ++l) sa.sdf_h[l] = Dl(l);
@@ -341,30 +263,29 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
     } else {
     auto sp_fwd = [&](int l, int K, float* pingpong) -> int {
       float* out = sph ? Dl(l) : pingpong;
-      const int r = g.fwd_sp(out, WN(l), K, tp[3 * l], l == 0 ? a.Xs0 : hin, l == 0 ? 40 : 256, sph ? nullptr : Dl(l));
+      const int r = g.fwd_sp(out, WN[l], K, tp[3 * l], l == 0 ? a.Xs0 : hin, l == 0 ? 40 : 256, sph ? nullptr : Dl(l));
       hin = out;
       return r;
     };
     ANR_TRY(sp_fwd(0, 39, Ha));
     ANR_TRY(sp_fwd(1, 256, Hb));
     ANR_TRY(sp_fwd(2, 256, Ha));
-    ANR_TRY(g.fwd(a.X4, 256, 217, WN(3), 256, tp[9], hin, 256, 256, 0, false, Dl(3), sqrt2, sph));
+    ANR_TRY(g.fwd(a.X4, 256, 217, WN[3], 256, tp[9], hin, 256, 256, 0, false, Dl(3), sqrt2, sph));
     hin = a.X4;
     ANR_TRY(sp_fwd(4, 256, Ha));
     ANR_TRY(sp_fwd(5, 256, Hb));
     ANR_TRY(sp_fwd(6, 256, Ha));
     ANR_TRY(sp_fwd(7, 256, Hb));
-    ANR_TRY(g.fwd(F(L.Y8), 264, 257, WN(8), 256, tp[24], hin, 256, 256, 0, false));
+    ANR_TRY(g.fwd(F(L.Y8), 264, 257, WN[8], 256, tp[24], hin, 256, 256, 0, false));
     }
 
     // B4 gradient of sdf w.r.t. the canonical point (reverse mode through the stored factors / outputs)
     if (fused) {
       MlpArgs ga{};
-      ga.wimg = gimg;
-      ga.bias = (const float*)(gimg + wbytes(ANR_L_SREV0, ANR_SREV_LAYERS));
+      im.bind(ga, gimg, ANR_L_SREV0, ANR_SREV_LAYERS);
       for (int l = 0; l < 8; ++l) ga.sdf_h[l] = Dl(l);
       ga.x4 = a.X4;
-      ga.w8row = WN(8);
+      ga.w8row = WN[8];
       ga.gb = F(L.gB);
       ga.gc = Gc;
       ga.n_rows = cnt;
@@ -372,27 +293,27 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
     } else {
     g.spd_h = sph ? 1 : 0;
     a.d7_h = sph ? 1 : 0;
-    if (g.bwd_top(Gb, 256, 256, Dl(7), WN(8), 256, WN(7), 256, Dl(6), 256)) {
+    if (g.bwd_top(Gb, 256, 256, Dl(7), WN[8], 256, WN[7], 256, Dl(6), 256)) {
       ANR_TRY(check_launch("k_lgemm (sdf, fused top)"));
     } else {
       hipLaunchKernelGGL(k_sdf_gtop, dim3((unsigned)(((long)cnt * 256 + 255) / 256)), pb, 0, s, a);
       ANR_TRY(check_launch("k_sdf_gtop"));
-      ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN(7), 256, Dl(6), 256));
+      ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN[7], 256, Dl(6), 256));
     }
-    ANR_TRY(g.bwd(Ga, 256, 256, Gb, 256, 256, WN(6), 256, Dl(5), 256));
-    ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN(5), 256, Dl(4), 256));
+    ANR_TRY(g.bwd(Ga, 256, 256, Gb, 256, 256, WN[6], 256, Dl(5), 256));
+    ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN[5], 256, Dl(4), 256));
     if (sph) {  // lin3's outputs h3 / sqrt2 in X4
       g.spd_scale = sqrt2;
-      ANR_TRY(g.bwd(Gc, 256, 256, Gb, 256, 256, WN(4), 256, a.X4, 217, sqrt2));
+      ANR_TRY(g.bwd(Gc, 256, 256, Gb, 256, 256, WN[4], 256, a.X4, 217, sqrt2));
       g.spd_scale = 0.f;
     } else {
-      ANR_TRY(g.bwd(Gc, 256, 256, Gb, 256, 256, WN(4), 256, Dl(3), 217, sqrt2));
+      ANR_TRY(g.bwd(Gc, 256, 256, Gb, 256, 256, WN[4], 256, Dl(3), 217, sqrt2));
     }
-    ANR_TRY(g.bwd(Ga, 256, 256, Gc, 256, 217, WN(3), 256, Dl(2), 256));
-    ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN(2), 256, Dl(1), 256));
-    ANR_TRY(g.bwd(Ga, 256, 256, Gb, 256, 256, WN(1), 256, Dl(0), 256));
+    ANR_TRY(g.bwd(Ga, 256, 256, Gc, 256, 217, WN[3], 256, Dl(2), 256));
+    ANR_TRY(g.bwd(Gb, 256, 256, Ga, 256, 256, WN[2], 256, Dl(1), 256));
+    ANR_TRY(g.bwd(Ga, 256, 256, Gb, 256, 256, WN[1], 256, Dl(0), 256));
     g.spd_h = 0;
-    ANR_TRY(g.bwd(F(L.gB), 40, 39, Ga, 256, 256, WN(0), 39, nullptr, 0));
+    ANR_TRY(g.bwd(F(L.gB), 40, 39, Ga, 256, 256, WN[0], 39, nullptr, 0));
     }
     hipLaunchKernelGGL(k_sdf_gamma_bwd, pg, pb, 0, s, a);
     ANR_TRY(check_launch("k_sdf_gamma_bwd"));
@@ -400,8 +321,7 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
     // B6 colour network (color_latent folded into lin3)
     if (fused) {
       MlpArgs ca{};
-      ca.wimg = cimg;
-      ca.bias = (const float*)(cimg + wbytes(ANR_L_COL0, ANR_COL_LAYERS));
+      im.bind(ca, cimg, ANR_L_COL0, ANR_COL_LAYERS);
       ca.fold = fold;
       ca.ptb = a.C0;
       ca.ptb_ld = 40;
@@ -410,14 +330,14 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
       ca.n_rows = cnt;
       if (launch_color(ca, cus, s, x6) != 0) return fail(ANR_E_HIP, "k_color launch failed");
     } else {
-    ANR_TRY(g.fwd(Ha, 256, 256, WN(9), 289, tp[29], a.C0, 40, 33, 0, true, nullptr, 0.f, false, F(L.Y8) + 1, 264, 256, 33));
-    ANR_TRY(g.fwd(Hb, 256, 256, WN(10), 256, tp[32], Ha, 256, 256, 0, true));
-    ANR_TRY(g.fwd(Ha, 256, 256, WN(11), 256, tp[35], Hb, 256, 256, 0, true));
-    if (g.fwd_head(F(L.Yc), 4, 3, WN(13), tp[41], WN(12), 384, fold + 512, Ha, 256, 256)) {
+    ANR_TRY(g.fwd(Ha, 256, 256, WN[9], 289, tp[29], a.C0, 40, 33, 0, true, nullptr, 0.f, false, F(L.Y8) + 1, 264, 256, 33));
+    ANR_TRY(g.fwd(Hb, 256, 256, WN[10], 256, tp[32], Ha, 256, 256, 0, true));
+    ANR_TRY(g.fwd(Ha, 256, 256, WN[11], 256, tp[35], Hb, 256, 256, 0, true));
+    if (g.fwd_head(F(L.Yc), 4, 3, WN[13], tp[41], WN[12], 384, fold + 512, Ha, 256, 256)) {
       ANR_TRY(check_launch("k_lgemm (sdf, colour lin3 + lin4)"));
     } else {
-      ANR_TRY(g.fwd(Hb, 256, 256, WN(12), 384, fold + 512, Ha, 256, 256, 0, true));
-      ANR_TRY(g.fwd(F(L.Yc), 4, 3, WN(13), 256, tp[41], Hb, 256, 256, 0, false));
+      ANR_TRY(g.fwd(Hb, 256, 256, WN[12], 384, fold + 512, Ha, 256, 256, 0, true));
+      ANR_TRY(g.fwd(F(L.Yc), 4, 3, WN[13], 256, tp[41], Hb, 256, 256, 0, false));
     }
     }
 
@@ -450,7 +370,7 @@ int check_points(const anr_sdf_params* p, const anr_sdf_frame* f, const anr_samp
   if (!f->A || !f->big_A || !f->R || !f->Th || !f->poses || !f->pvertices || !f->weights || !f->tbounds ||
       !f->latent_index)
     return fail(ANR_E_ARG, "sdf network: NULL frame tensor");
-  if (f->n_verts <= 0 || f->n_verts > 6912) return fail(ANR_E_ARG, "sdf network: n_verts must be in [1, 6912]");
+  if (!n_verts_ok(f->n_verts)) return fail(ANR_E_ARG, "sdf network: n_verts must be in [1, 6912]");
   if (f->n_views) return fail(ANR_E_ARG, "sdf network: the visibility filter is a renderer option (n_views must be 0)");
   return ANR_OK;
 }
@@ -488,50 +408,33 @@ int anr_sdf_network_fwd(const anr_sdf_params* p, const anr_sdf_frame* f, const a
 const int32_t* anr_sdf_network_counts(const void* workspace, int n) {
   if (!workspace || n <= 0) return nullptr;
   const int G = groups_of(n);
-  return (const int32_t*)((const char*)workspace + slayout(G, G).counts);
+  return (const int32_t*)((const char*)workspace + slayout(G, G).F.counts);
 }
 
-// KNN blend of free points: [R | Th identity (12 floats)] [mask (G x 8)] [chunk_min 8] [knn (64 G x 32)]
-//   [raw (64 G x 16)] [sdf (64 G x 4)]
+// KNN blend of free points: the free-point search's regions (KnnFreeLayout)
 size_t anr_knn_blend_workspace_bytes(int n) {
   if (n <= 0) return 0;
-  const size_t G = (size_t)groups_of(n);
-  return align256(64) + align256(G * 8) + align256(8) + align256(64 * G * 32) + align256(64 * G * 16) + align256(64 * G * 4);
+  Carve c;
+  KnnFreeLayout L{};
+  L.carve(c, (size_t)groups_of(n));
+  return c.o;
 }
 
 int anr_knn_blend(const float* verts, const float* weights, int nv, const float* pts, int n, float norm_th, float* bw,
                   uint8_t* inside, void* workspace, size_t ws_bytes, void* stream) {
   if (!verts || !weights || !pts || !workspace || n <= 0 || (!bw && !inside))
     return fail(ANR_E_ARG, "anr_knn_blend: bad arguments");
-  if (nv <= 0 || nv > 6912) return fail(ANR_E_ARG, "anr_knn_blend: nv must be in [1, 6912]");
+  if (!n_verts_ok(nv)) return fail(ANR_E_ARG, "anr_knn_blend: nv must be in [1, 6912]");
   if (ws_bytes < anr_knn_blend_workspace_bytes(n)) return fail(ANR_E_WORKSPACE, "anr_knn_blend: workspace too small");
   hipStream_t s = (hipStream_t)stream;
-  const int G = groups_of(n);
-  char* w = (char*)workspace;
-  float* rt = (float*)w;
-  w += align256(64);
-  uint64_t* mask = (uint64_t*)w;
-  w += align256((size_t)G * 8);
-  uint64_t* cmin = (uint64_t*)w;
-  w += align256(8);
-  uint32_t* knn = (uint32_t*)w;
-  w += align256((size_t)64 * G * 32);
-  float4* raw = (float4*)w;
-  w += align256((size_t)64 * G * 16);
-  float* sdf = (float*)w;
-  static const float ident[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-  if (hipMemcpyAsync(rt, ident, sizeof(ident), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemsetAsync(cmin, 0xff, 8, s) != hipSuccess)
-    return fail(ANR_E_HIP, "anr_knn_blend: setup");
-  SdfFrontArgs fa{};
-  fa.wpts = pts; fa.n_pts = n; fa.n_rays = G; fa.chunk = G;
-  fa.R = rt; fa.Th = rt + 9;  // world -> pose with R = I, Th = 0 is the identity in fp32 (x * 1 + y * 0 + z * 0)
-  fa.verts = verts; fa.nv = nv; fa.norm_th = norm_th;
-  fa.mask = mask; fa.chunk_min = cmin; fa.knn = knn; fa.raw = raw; fa.sdf = sdf;
-  hipLaunchKernelGGL(k_sdf_front, dim3(std::min(sdf_cus(), (G + 15) / 16)), dim3(1024), 0, s, fa);
-  ANR_TRY(check_launch("k_sdf_front (knn blend)"));
-  hipLaunchKernelGGL(k_knn_blend_out, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t*)knn, (const uint64_t*)mask,
-                     weights, n, bw, inside);
+  char* ws = (char*)workspace;
+  Carve c;
+  KnnFreeLayout L{};
+  L.carve(c, (size_t)groups_of(n));
+  ANR_TRY(knn_free_setup(ws, L, "anr_knn_blend", s));
+  ANR_TRY(knn_free_points(ws, L, pts, n, verts, nv, norm_th, "knn blend", s));
+  hipLaunchKernelGGL(k_knn_blend_out, dim3((n + 255) / 256), dim3(256), 0, s, (const uint32_t*)(ws + L.knn),
+                     (const uint64_t*)(ws + L.mask), weights, n, bw, inside);
   return check_launch("k_knn_blend_out");
 }
 

@@ -27,6 +27,7 @@
 #include "../../include/aninerf.h"
 #include "anr_common.h"
 #include "anr_kernels.h"
+#include "anr_knn_host.h"
 #include "anr_sdf.h"
 #include "anr_train.h"
 #include "anr_ws.h"
@@ -909,9 +910,8 @@ int sdf_train_core(const TrainCore& C) {
   float* sdf = net_fwd ? C.sdf_out : F(L.sdf);
   float* acc = F(L.acc);
   float* acc3 = F(L.acc3);
-  if (hipMemsetAsync(ws + L.counts, 0, 16, s) != hipSuccess ||
-      hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess ||
-      hipMemsetAsync(ws + L.inv, 0xff, (size_t)N * 4, s) != hipSuccess || hipMemsetAsync(acc, 0, 64, s) != hipSuccess ||
+  // (counts and chunk_min: knn_front_compact's presets; PTS, which has no front-end, presets them below)
+  if (hipMemsetAsync(ws + L.inv, 0xff, (size_t)N * 4, s) != hipSuccess || hipMemsetAsync(acc, 0, 64, s) != hipSuccess ||
       hipMemsetAsync(acc3, 0, 16, s) != hipSuccess || hipMemsetAsync(F(L.dbeta), 0, 16, s) != hipSuccess ||
       hipMemsetAsync(ws + L.zero, 0, 64, s) != hipSuccess ||
       hipMemsetAsync(F(L.dWe), 0, SDF_WN_FLOATS * 4, s) != hipSuccess)
@@ -923,42 +923,29 @@ int sdf_train_core(const TrainCore& C) {
   hipLaunchKernelGGL(k_sdf_wnorm, dim3(sdf_wn_rows()), dim3(256), 0, s, T, wimg);
   hipLaunchKernelGGL(k_sdf_fold, dim3(3), dim3(256), 0, s, T, (const float*)wimg, f->poses, f->latent_index, fold);
   const bool pts = C.mode == PTS;
-  if (!pts)
-    hipLaunchKernelGGL(k_sdf_tbtab, dim3(1), dim3(64), 0, s, f->tbounds, nch, tbtab,
-                       step ? C.out->tbounds_out : (net_fwd ? C.tb_out : nullptr));
   ANR_TRY(check_launch("sdf train prep"));
 
-  // ---- B1 front-end (KNN keep mask) + ordered compaction; one host read of n'
+  // ---- B1 front-end (KNN keep mask) + ordered compaction (anr_knn_host.h); one host read of n'
   SdfFrontArgs fa{};
   fa.ray_o = ray_o; fa.ray_d = ray_d; fa.near_ = near_; fa.far_ = far_; fa.t_rand = o->t_rand;
   fa.wpts = C.wpts; fa.n_pts = C.n_pts;
   fa.n_rays = R; fa.chunk = C.chunk; fa.R = f->R; fa.Th = f->Th; fa.verts = f->pvertices; fa.nv = f->n_verts;
-  fa.norm_th = o->norm_th; fa.mask = (uint64_t*)(ws + L.mask); fa.chunk_min = (uint64_t*)(ws + L.chunk_min);
-  fa.knn = (uint32_t*)(ws + L.knn); fa.raw = raw; fa.sdf = sdf;
-  int cus = 256;
-  {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      cus = v;
-  }
-  CompactArgs ca{};
+  fa.norm_th = o->norm_th; fa.knn = (uint32_t*)(ws + L.knn); fa.raw = raw; fa.sdf = sdf;
+  const int cus = num_cus();
+  const int* list = pts ? nullptr : (const int*)(ws + L.list);
   int n = 0;
   int* inv = (int*)(ws + L.inv);
   if (pts) {
     n = C.n_pts;
+    if (hipMemsetAsync(ws + L.counts, 0, 16, s) != hipSuccess ||
+        hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess)
+      return fail(ANR_E_HIP, "sdf train: memset");
   } else {
-    hipLaunchKernelGGL(k_sdf_front, dim3(std::min(cus, (R + 15) / 16)), dim3(1024), 0, s, fa);
-    ANR_TRY(check_launch("k_sdf_front (train)"));
-    ca.n_rays = R; ca.chunk = C.chunk; ca.mask = fa.mask; ca.chunk_min = fa.chunk_min;
-    ca.ray_off = (int*)(ws + L.ray_off); ca.block_sum = (int*)(ws + L.block_sum); ca.list = (int*)(ws + L.list);
-    const int nb = (R + 255) / 256;
-    hipLaunchKernelGGL(k_count, dim3(nb), dim3(256), 0, s, ca);
-    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, ca.block_sum, nb, counts);
-    hipLaunchKernelGGL(k_compact, dim3((R + 3) / 4), dim3(256), 0, s, ca);
-    ANR_TRY(check_launch("k_compact (sdf train)"));
+    const KnnFrontLayout FL{L.counts, L.mask, L.chunk_min, L.ray_off, L.block_sum, L.list, L.knn, L.tbtab};
+    ANR_TRY(knn_front_compact(fa, ws, FL, f->tbounds, step ? C.out->tbounds_out : (net_fwd ? C.tb_out : nullptr), false,
+                              "sdf train", s, nullptr));
     ANR_TRY(read_int(counts, &n, s));
-    hipLaunchKernelGGL(k_st_inv, dim3((n + 255) / 256 + 1), dim3(256), 0, s, (const int*)ca.list, (const int*)counts, inv);
+    hipLaunchKernelGGL(k_st_inv, dim3((n + 255) / 256 + 1), dim3(256), 0, s, list, (const int*)counts, inv);
   }
 
   TG g{s};
@@ -1038,7 +1025,7 @@ int sdf_train_core(const TrainCore& C) {
   const int rin[8] = {135, 256, 256, 256, 256, 391, 256, 256};
 
   SdfPointArgs a{};
-  a.list = ca.list; a.b0 = 0; a.cnt = n;
+  a.list = list; a.b0 = 0; a.cnt = n;
   a.ray_o = ray_o; a.ray_d = ray_d; a.near_ = near_; a.far_ = far_; a.t_rand = o->t_rand; a.chunk = C.chunk;
   a.wpts = C.wpts; a.vdir = C.vdir; a.n_pts = C.n_pts;
   a.R = f->R; a.Th = f->Th; a.A = f->A; a.bigA = f->big_A; a.weights = f->weights; a.knn = fa.knn;
@@ -1305,7 +1292,7 @@ int sdf_train_core(const TrainCore& C) {
   if (n > 0 && !net_fwd) {
     // ---- backward: raw -> colour logits, sdf, beta; msk_sdf -> sdf
     StRaw sr{};
-    sr.list = ca.list; sr.n_kept = counts; sr.chunk = C.chunk; sr.draw = draw;
+    sr.list = list; sr.n_kept = counts; sr.chunk = C.chunk; sr.draw = draw;
     sr.C0 = F(L.C0); sr.tbtab = tbtab; sr.Y8 = F(L.Y8); sr.Yc = F(L.Yc); sr.beta = tp[SDF_BETA];
     sr.dYc = F(L.dYc); sr.ds = F(L.ds); sr.dbeta = F(L.dbeta); sr.dbeta_part = lpart(4);
     hipLaunchKernelGGL(k_st_raw_bwd, pg, pb, 0, s, sr);
@@ -1316,7 +1303,7 @@ int sdf_train_core(const TrainCore& C) {
                          (const uint8_t*)(ws + L.rflag), (const int*)inv, R, alpha, F(L.ds), acc, lpart(3));
       if (det) det_sum(3, 0, 1, gm, acc + 3);
     } else if (C.d_sdf)
-      hipLaunchKernelGGL(k_st_cotan_sdf, pg, pb, 0, s, (const int*)ca.list, (const int*)counts, C.d_sdf, F(L.ds));
+      hipLaunchKernelGGL(k_st_cotan_sdf, pg, pb, 0, s, list, (const int*)counts, C.d_sdf, F(L.ds));
     ANR_TRY(check_launch("sdf train: raw / msk backward"));
     // ---- colour net backward (weight-normed lin4..lin0; color_latent folded into lin3)
     part(8);

@@ -663,8 +663,6 @@ int bw_forward(Exec& e, const float* const* W, const float* G, float* H, float* 
 // the latent-column gradients of layers 0 and 5. Issued one layer per step() on stream st, so that two
 // chains on two streams can be issued alternately: the host spends ~4 API calls per layer and would
 // otherwise reach the second chain only after the first one's whole issue (profiles/r3l trace).
-int chain_cus();
-
 struct BwBackward {
   Exec& e;
   hipStream_t st;
@@ -763,7 +761,7 @@ struct BwBackward {
     a.M_dev = e.n_dev;
     ANR_TRY(e.guard_pending(dY0, 16 * dstride / N, true));  // the 8 gradient slots (dstride floats each)
     ANR_TRY(e.guard_pending(dG, 64, false));
-    if (tchain_run(2, a, e.grid_n(), chain_cus(), st) != 0) return check_launch("k_tchain_bwb");
+    if (tchain_run(2, a, e.grid_n(), num_cus(), st) != 0) return check_launch("k_tchain_bwb");
     return ANR_OK;
   }
 };
@@ -829,15 +827,6 @@ bool chains_cover(const Exec& e, bool fwd, bool bwd) {
 unsigned char* tc_img(unsigned char* base, int prog) {
   for (int k = 0; k < prog; ++k) base += tchain_image_bytes(k);
   return base;
-}
-int chain_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int d = 0, v = 0;
-    cus = hipGetDevice(&d) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, d) == hipSuccess && v > 0
-              ? v : 256;
-  }
-  return cus;
 }
 // pack the BW (program 0) and NeRF (program 1) images from this call's weights
 int chain_pack(const anr_params* p, unsigned char* img, hipStream_t s) {
@@ -926,7 +915,7 @@ int chain_bw(const Exec& e, const anr_params* p, const unsigned char* img, const
   }
   a.mem = (const unsigned short*)G; a.ld_mem = 64; a.kmem_cols = 63;
   a.M_dev = e.n_dev;
-  if (tchain_run(0, a, e.grid_n(), chain_cus(), s) != 0) return check_launch("k_tchain_bw");
+  if (tchain_run(0, a, e.grid_n(), num_cus(), s) != 0) return check_launch("k_tchain_bw");
   return ANR_OK;
 }
 
@@ -1073,7 +1062,7 @@ int train_forward(const TrainCall& c, const anr_render_out* out, hipStream_t s, 
     a.mem = (const unsigned short*)b.Gt; a.ld_mem = 64; a.kmem_cols = 63;
     a.mem2 = (const unsigned short*)b.Gv; a.ld_mem2 = 64; a.kmem2_cols = 27;
     a.M_dev = e.n_dev;
-    if (tchain_run(1, a, e.grid_n(), chain_cus(), s) != 0) return check_launch("k_tchain_nf");
+    if (tchain_run(1, a, e.grid_n(), num_cus(), s) != 0) return check_launch("k_tchain_nf");
   } else {
     const unsigned h = e.hb ? (BF_A | BF_C) : 0, a = e.hb ? BF_A : 0;  // gamma, H, Feat, Lat bf16 under e.hb
     ANR_TRY(e.fwd(Hn, 256, 256, PT(1), 63, PT(2), true, b.Gt, 64, 63, 0, nullptr, 0, 0, 0, h));
@@ -1202,7 +1191,7 @@ int train_backward(const TrainCall& c, float* const* g, const float* d_rgb, cons
     a.M_dev = e.n_dev;
     ANR_TRY(e.guard_pending(dHn, 16 * S / N, true));
     ANR_TRY(e.guard_pending(b.dGt, 64, false));
-    if (tchain_run(3, a, e.grid_n(), chain_cus(), s) != 0) return check_launch("k_tchain_nfb");
+    if (tchain_run(3, a, e.grid_n(), num_cus(), s) != 0) return check_launch("k_tchain_nfb");
   }
   // rgb_fc, view_fc (ReLU), latent_fc (latent folded), feature_fc || alpha_fc
   ANR_TRY(e.wgrad(g[25], 128, 0, 3, b.dRgb, 4, View, 128, 128, g[26]));

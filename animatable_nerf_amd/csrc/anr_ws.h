@@ -81,6 +81,8 @@ inline Layout layout_image(int n_rays, int chunk, long np, bool need_raw) {
 
 int fail(int code, const std::string& msg);
 int check_launch(const char* what);
+// compute units of the current device, cached per device (256 where the query fails)
+int num_cus();
 #define ANR_TRY(x)                  \
   do {                              \
     const int _rc = (x);            \

@@ -22,52 +22,22 @@ import torch
 
 from . import _lib
 from . import config as _config
+from .renderer_knn import KnnRenderer, _f32, render_precision
 
 CHUNK = 2048
 RAY_KEYS = ('ray_o', 'ray_d', 'near', 'far')
 FRAME_KEYS = ('A', 'big_A', 'R', 'Th', 'pvertices', 'tvertices', 'weights', 'tbounds')
 
 
-def _f32(t, device):
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
 def _lbw_precision(cfg):
-    rprec = cfg.get('render_precision', 'fp32')
-    precs = {'fp32': _lib.FP32, 'bf16x3': _lib.BF16X3, 'bf16x6': _lib.BF16X6}
-    if rprec not in precs:
-        raise ValueError(f"renderer_lbw: render_precision must be one of {sorted(precs)}, got {rprec!r}")
-    return precs[rprec]
+    return render_precision(cfg, 'renderer_lbw: ')
 
 
-class Renderer:
+class Renderer(KnnRenderer):
     widens_tbounds = True  # per chunk, in place (aligned_aninerf_lbw_network.py:124-126)
-
-    def __init__(self, net, cfg=None):
-        self.net = net
-        self.cfg = cfg if cfg is not None else _config.active()
-        self.lib = _lib.load()
-        self._ws = None
-        self._pcache = None
-        self.last_counts = None
-
-    def device(self):
-        return next(self.net.parameters()).device
-
-    def params(self):
-        key = tuple(t.data_ptr() for t in self.net.tensors())
-        if self._pcache is not None and self._pcache[0] == key:
-            return self._pcache[1]
-        ts = [t.detach() for t in self.net.tensors()]
-        if ts[0].device.type != 'cuda':
-            raise RuntimeError('Renderer: the network must be on a GPU (net.cuda()); there is no CPU path')
-        p = _lib.LbwParams()
-        for i, t in enumerate(ts):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError('Renderer: parameters must be contiguous float32')
-            p.t[i] = t.data_ptr()
-        self._pcache = (key, p)
-        return p
+    params_type = _lib.LbwParams
+    name = 'renderer_lbw'
+    counts_fn, knn_fn, kept_fn = 'anr_lbw_render_counts', 'anr_lbw_render_knn', 'anr_lbw_render_kept'
 
     def render_device(self, batch, t_rand=None, image_only=False):
         """All outputs stay in HBM; ``batch['tbounds']`` is widened in place (reference quirk). ``t_rand`` (R, 64):
@@ -85,14 +55,9 @@ class Renderer:
         if t_rand is None and cfg.perturb > 0 and self.net.training:
             t_rand = torch.rand((R, ns), device=dev)
         rays = {k: _f32(batch[k], dev) for k in RAY_KEYS}
-        fr = {k: _f32(batch[k], dev) for k in FRAME_KEYS}
-        tr = None if t_rand is None else _f32(t_rand, dev).reshape(R, ns)
-        li = batch['latent_index'].to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
         f = _lib.LbwFrame()
-        for k in FRAME_KEYS:
-            setattr(f, k, fr[k].data_ptr())
-        f.n_verts = fr['pvertices'].shape[-2]
-        f.latent_index = li.data_ptr()
+        fr = self.fill_frame(f, batch, FRAME_KEYS, dev)  # (kept alive over the call)
+        tr = None if t_rand is None else _f32(t_rand, dev).reshape(R, ns)
         o = _lib.RenderOpts()
         o.n_samples, o.chunk = ns, int(cfg.get('chunk', CHUNK))
         o.norm_th, o.train_th = float(cfg.norm_th), float(cfg.train_th)
@@ -107,9 +72,7 @@ class Renderer:
         tb_out = torch.empty((2, 3), device=dev)
         out = _lib.LbwRenderOut(rgb.data_ptr(), acc.data_ptr(), depth.data_ptr(), raw.data_ptr(), tb_out.data_ptr())
         ws_bytes = self.lib.anr_lbw_render_workspace_bytes(R, ctypes.byref(o), img)
-        if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = self.workspace(ws_bytes, dev)
         st = _lib.stream_ptr(dev)
         _lib.check(self.lib.anr_lbw_render_fwd(ctypes.byref(p), ctypes.byref(f), *[_lib.ptr(rays[k]) for k in RAY_KEYS],
                                                R, ctypes.byref(o), ctypes.byref(out), img, _lib.ptr(ws), ws_bytes, st),
@@ -131,29 +94,6 @@ class Renderer:
                                                 _lib.ptr(self.last_row_ids), st), 'anr_lbw_render_rows')
         ret.update({'pbw': pbw, 'tbw': tbw})
         return ret
-
-    def knn_records(self):
-        """(R*64, 8) int32 view of the last render's first-search KNN records (anr_lbw_render_knn): w0..w4 float
-        bits, then the five vertex indices packed as i0 | i1 << 16, i2 | i3 << 16, i4 (tests, debugging)."""
-        R, o, img = self._last
-        addr = self.lib.anr_lbw_render_knn(_lib.ptr(self._ws), R, ctypes.byref(o), img)
-        if not addr:
-            raise RuntimeError('anr_lbw_render_knn: no records')
-        off = addr - self._ws.data_ptr()
-        return self._ws[off:off + R * 64 * 32].view(torch.int32).view(R * 64, 8)
-
-    def _view(self, fn, nbytes):
-        R, o, img = self._last
-        addr = fn(_lib.ptr(self._ws), R, ctypes.byref(o), img)
-        if not addr:
-            raise RuntimeError('renderer_lbw: no workspace view')
-        off = addr - self._ws.data_ptr()
-        return self._ws[off:off + nbytes]
-
-    def kept_ids(self):
-        """(n',) int32 sample ids (ray * 64 + sample) the last render kept, in order (tests, debugging)."""
-        n = int(self._view(self.lib.anr_lbw_render_counts, 4).view(torch.int32).item())
-        return self._view(self.lib.anr_lbw_render_kept, n * 4).view(torch.int32).clone()
 
     def warped(self, n):
         """(tpose (n,3), tpose_dirs (n,3)) of the first n rows of the last render's last batch (tests, debugging)."""

@@ -24,6 +24,7 @@ import torch
 
 from . import _lib
 from . import config as _config
+from .renderer_knn import KnnRenderer, _f32, render_precision
 
 CHUNK = 2048
 ALPHA_CHUNK = 2048 * 64  # aninerf_mesh_renderer.py:36
@@ -31,47 +32,17 @@ RAY_KEYS = ('ray_o', 'ray_d', 'near', 'far')
 FRAME_KEYS = ('A', 'big_A', 'R', 'Th', 'pvertices', 'weights', 'poses', 'tbounds')
 
 
-def _f32(t, device):
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
 def _pdf_precision(cfg):
-    rprec = cfg.get('render_precision', 'fp32')
-    precs = {'fp32': _lib.FP32, 'bf16x3': _lib.BF16X3, 'bf16x6': _lib.BF16X6}
-    if rprec not in precs:
-        raise ValueError(f"renderer_pdf: render_precision must be one of {sorted(precs)}, got {rprec!r}")
-    return precs[rprec]
+    return render_precision(cfg, 'renderer_pdf: ')
 
 
-class Renderer:
+class Renderer(KnnRenderer):
     widens_tbounds = True      # per chunk, in place (aligned_aninerf_pdf_network.py:125-127)
     visibility_filter = False  # renderer_pdf_mmsk: the training-view visibility filter of tpose_renderer_mmsk
-
-    def __init__(self, net, cfg=None):
-        self.net = net
-        self.cfg = cfg if cfg is not None else _config.active()
-        self.lib = _lib.load()
-        self._ws = None
-        self._pcache = None
-        self.last_counts = None
-
-    def device(self):
-        return next(self.net.parameters()).device
-
-    def params(self):
-        key = tuple(t.data_ptr() for t in self.net.tensors())
-        if self._pcache is not None and self._pcache[0] == key:
-            return self._pcache[1]
-        ts = [t.detach() for t in self.net.tensors()]
-        if ts[0].device.type != 'cuda':
-            raise RuntimeError('Renderer: the network must be on a GPU (net.cuda()); there is no CPU path')
-        p = _lib.PdfParams()
-        for i, t in enumerate(ts):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError('Renderer: parameters must be contiguous float32')
-            p.t[i] = t.data_ptr()
-        self._pcache = (key, p)
-        return p
+    params_type = _lib.PdfParams
+    name = 'renderer_pdf'
+    counts_fn, knn_fn, kept_fn = 'anr_pdf_render_counts', 'anr_pdf_render_knn', 'anr_pdf_render_kept'
+    _aws = None  # alpha_points' workspace
 
     def check_cfg(self):
         cfg = self.cfg
@@ -98,20 +69,10 @@ class Renderer:
         if t_rand is None and cfg.perturb > 0 and self.net.training:
             t_rand = torch.rand((R, ns), device=dev)
         rays = {k: _f32(batch[k], dev) for k in RAY_KEYS}
-        fr = {k: _f32(batch[k], dev) for k in FRAME_KEYS}
-        tr = None if t_rand is None else _f32(t_rand, dev).reshape(R, ns)
-        li = batch['latent_index'].to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
         f = _lib.PdfFrame()
-        for k in FRAME_KEYS:
-            setattr(f, k, fr[k].data_ptr())
-        f.n_verts = fr['pvertices'].shape[-2]
-        f.latent_index = li.data_ptr()
-        if self.visibility_filter:  # tpose_renderer_mmsk.py:14-57 on the device
-            views = {k: _f32(batch[k], dev) for k in ('Ks', 'RT')}
-            views['msks'] = batch['msks'].to(device=dev, dtype=torch.uint8).contiguous()
-            f.n_views = int(views['Ks'].shape[1])
-            f.Ks, f.RT, f.msks = views['Ks'].data_ptr(), views['RT'].data_ptr(), views['msks'].data_ptr()
-            f.img_h, f.img_w = int(batch['H']), int(batch['W'])
+        fr = self.fill_frame(f, batch, FRAME_KEYS, dev)  # (kept alive over the call)
+        tr = None if t_rand is None else _f32(t_rand, dev).reshape(R, ns)
+        views = self.fill_views(f, batch, dev) if self.visibility_filter else None  # (kept alive)
         o = _lib.RenderOpts()
         o.n_samples, o.chunk = ns, int(cfg.get('chunk', CHUNK))
         o.norm_th, o.train_th = float(cfg.norm_th), float(cfg.train_th)  # neither is read by this network
@@ -126,9 +87,7 @@ class Renderer:
         tb_out = torch.empty((2, 3), device=dev)
         out = _lib.PdfRenderOut(rgb.data_ptr(), acc.data_ptr(), depth.data_ptr(), raw.data_ptr(), tb_out.data_ptr())
         ws_bytes = self.lib.anr_pdf_render_workspace_bytes(R, ctypes.byref(o), img)
-        if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = self.workspace(ws_bytes, dev)
         st = _lib.stream_ptr(dev)
         _lib.check(self.lib.anr_pdf_render_fwd(ctypes.byref(p), ctypes.byref(f), *[_lib.ptr(rays[k]) for k in RAY_KEYS],
                                                R, ctypes.byref(o), ctypes.byref(out), img, _lib.ptr(ws), ws_bytes, st),
@@ -159,11 +118,10 @@ class Renderer:
         alpha = torch.zeros(n, device=dev)
         if n == 0:
             return alpha
-        keys = ('A', 'big_A', 'R', 'Th', 'pvertices', 'weights', 'poses')
-        fr = {k: _f32(batch[k], dev) for k in keys}
         f = _lib.PdfFrame()
-        for k in keys:
-            setattr(f, k, fr[k].data_ptr())
+        fr = {k: _f32(batch[k], dev) for k in ('A', 'big_A', 'R', 'Th', 'pvertices', 'weights', 'poses')}
+        for k, t in fr.items():
+            setattr(f, k, t.data_ptr())
         f.n_verts = fr['pvertices'].shape[-2]
         o = _lib.AlphaOpts()
         o.chunk_pts, o.norm_th, o.novel_pose, o.precision = int(chunk_pts), 0.1, 0, _pdf_precision(self.cfg)
@@ -177,27 +135,6 @@ class Renderer:
                                                  _lib.ptr(alpha), _lib.ptr(self._aws), nbytes, _lib.stream_ptr(dev)),
                    'anr_pdf_alpha_points')
         return alpha
-
-    _aws = None
-
-    def _view(self, fn, nbytes):
-        R, o, img = self._last
-        addr = fn(_lib.ptr(self._ws), R, ctypes.byref(o), img)
-        if not addr:
-            raise RuntimeError('renderer_pdf: no workspace view')
-        off = addr - self._ws.data_ptr()
-        return self._ws[off:off + nbytes]
-
-    def knn_records(self):
-        """(R*64, 8) int32 view of the last render's KNN records (anr_pdf_render_knn): w0..w4 float bits, then the
-        five vertex indices packed as i0 | i1 << 16, i2 | i3 << 16, i4 (tests, debugging)."""
-        R = self._last[0]
-        return self._view(self.lib.anr_pdf_render_knn, R * 64 * 32).view(torch.int32).view(R * 64, 8)
-
-    def kept_ids(self):
-        """(n',) int32 sample ids (ray * 64 + sample) the last render kept, in order (tests, debugging)."""
-        n = int(self._view(self.lib.anr_pdf_render_counts, 4).view(torch.int32).item())
-        return self._view(self.lib.anr_pdf_render_kept, n * 4).view(torch.int32).clone()
 
     def warped(self, n):
         """(init_bigpose (n,3), tpose (n,3), tpose_dirs (n,3)) of the first n rows of the last render's last batch

@@ -20,6 +20,7 @@ import torch
 from . import _lib
 from . import config as _config
 from .renderer import _cfg_deterministic
+from .renderer_knn import KnnRenderer, _f32, render_precision
 
 CHUNK = 2048
 RAY_KEYS = ('ray_o', 'ray_d', 'near', 'far')
@@ -27,19 +28,11 @@ FRAME_KEYS = ('A', 'big_A', 'R', 'Th', 'poses', 'pvertices', 'weights', 'tbounds
 NORM_TH = 0.1  # anisdf_pdf_network.py:172 (hard-coded, not cfg.norm_th)
 
 
-def _f32(t, device):
-    return t.to(device=device, dtype=torch.float32).contiguous()
-
-
 def _sdf_precision(cfg):
     """cfg.render_precision (include/aninerf.h anr_render_opts.precision): 'fp32' exact fp32 MFMA layer
     GEMMs; 'bf16x3' the four fused launches in split bf16 (hi/lo, 3 products per multiply-add); 'bf16x6'
     the fused launches with hi/mid/lo bf16 (6 products, fp32-level, libm-grade softplus)."""
-    rprec = cfg.get('render_precision', 'fp32')
-    precs = {'fp32': _lib.FP32, 'bf16x3': _lib.BF16X3, 'bf16x6': _lib.BF16X6}
-    if rprec not in precs:
-        raise ValueError(f"render_precision must be one of {sorted(precs)}, got {rprec!r}")
-    return precs[rprec]
+    return render_precision(cfg)
 
 
 def widen_tbounds(tbounds, k):
@@ -52,37 +45,12 @@ def widen_tbounds(tbounds, k):
     return tb.reshape(tbounds.shape).contiguous()
 
 
-class Renderer:
+class Renderer(KnnRenderer):
     widens_tbounds = True  # per chunk, in place (anisdf_pdf_network.py:204-206)
     visibility_filter = False  # renderer_sdf_mmsk.Renderer turns it on
-
-    def __init__(self, net, cfg=None):
-        self.net = net
-        self.cfg = cfg if cfg is not None else _config.active()
-        self.lib = _lib.load()
-        self._ws = None
-        self._pcache = None  # (parameter pointers, SdfParams) of the last call
-        self.last_counts = None
-
-    def device(self):
-        return next(self.net.parameters()).device
-
-    def params(self):
-        # per-call host work: the struct is rebuilt (detach + checks of 63 tensors, ~0.1 ms of Python that
-        # the GPU waits out at every training step's host sync) only when a parameter moved
-        key = tuple(t.data_ptr() for t in self.net.tensors())
-        if self._pcache is not None and self._pcache[0] == key:
-            return self._pcache[1]
-        ts = [t.detach() for t in self.net.tensors()]
-        if ts[0].device.type != 'cuda':
-            raise RuntimeError('Renderer: the network must be on a GPU (net.cuda()); there is no CPU path')
-        p = _lib.SdfParams()
-        for i, t in enumerate(ts):
-            if t.dtype != torch.float32 or not t.is_contiguous():
-                raise RuntimeError('Renderer: parameters must be contiguous float32')
-            p.t[i] = t.data_ptr()
-        self._pcache = (key, p)
-        return p
+    params_type = _lib.SdfParams
+    name = 'renderer_sdf'
+    counts_fn, knn_fn = 'anr_sdf_render_counts', 'anr_sdf_render_knn'
 
     def prepare(self, batch, t_rand=None, chunk_offset=0):
         """Device tensors and C structs of one call over ``batch`` (kept alive in the returned dict):
@@ -95,24 +63,16 @@ class Renderer:
         if t_rand is None and self.cfg.perturb > 0 and self.net.training:
             t_rand = torch.rand((R, ns), device=dev)
         rays = {k: _f32(batch[k], dev) for k in RAY_KEYS}
-        fr = {k: _f32(batch[k], dev) for k in FRAME_KEYS}
+        f = _lib.SdfFrame()
+        fr = self.fill_frame(f, batch, FRAME_KEYS, dev)
+        li = fr.pop('latent_index')
         if chunk_offset > 0:
             fr['tbounds'] = widen_tbounds(fr['tbounds'], chunk_offset)
+            f.tbounds = fr['tbounds'].data_ptr()
         tr = None if t_rand is None else _f32(t_rand, dev).reshape(R, ns)
-        li = batch['latent_index'].to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
         occ = batch['occupancy'].to(device=dev, dtype=torch.uint8).reshape(-1).contiguous()
-        f = _lib.SdfFrame()
-        for k in FRAME_KEYS:
-            setattr(f, k, fr[k].data_ptr())
-        f.n_verts = fr['pvertices'].shape[-2]
-        f.latent_index, f.occupancy = li.data_ptr(), occ.data_ptr()
-        views = {}
-        if self.visibility_filter:  # renderer_sdf_mmsk: tpose_renderer_mmsk.py:14-57 on the device
-            views = {k: _f32(batch[k], dev) for k in ('Ks', 'RT')}
-            views['msks'] = batch['msks'].to(device=dev, dtype=torch.uint8).contiguous()
-            f.n_views = int(views['Ks'].shape[1])
-            f.Ks, f.RT, f.msks = views['Ks'].data_ptr(), views['RT'].data_ptr(), views['msks'].data_ptr()
-            f.img_h, f.img_w = int(batch['H']), int(batch['W'])
+        f.occupancy = occ.data_ptr()
+        views = self.fill_views(f, batch, dev) if self.visibility_filter else {}  # renderer_sdf_mmsk
         o = _lib.RenderOpts()
         o.n_samples, o.chunk, o.norm_th, o.train_th = ns, int(self.cfg.get('chunk', CHUNK)), NORM_TH, 0.0
         o.t_rand = tr.data_ptr() if tr is not None else None
@@ -138,9 +98,7 @@ class Renderer:
         out = _lib.SdfRenderOut(rgb.data_ptr(), acc.data_ptr(), depth.data_ptr(), raw.data_ptr(), sdf.data_ptr(),
                                 tb_out.data_ptr())
         ws_bytes = self.lib.anr_sdf_render_workspace_bytes(R, ctypes.byref(o))
-        if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
-            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-        ws = self._ws
+        ws = self.workspace(ws_bytes, dev)
         st = _lib.stream_ptr(dev)
         _lib.check(self.lib.anr_sdf_render_fwd(ctypes.byref(p), ctypes.byref(f), *[_lib.ptr(rays[k]) for k in RAY_KEYS],
                                                R, ctypes.byref(o), ctypes.byref(out), _lib.ptr(ws), ws_bytes, st),
@@ -157,33 +115,20 @@ class Renderer:
                                                 _lib.ptr(msk_sdf), _lib.ptr(msk_label), st), 'anr_sdf_render_rows')
         with torch.no_grad():
             batch['tbounds'].copy_(tb_out.view_as(batch['tbounds']))
-        self._last_R, self._last_opts = R, o
+        self._last = (R, o)
         return {'raw': raw, 'sdf': sdf, 'resd': resd, 'gradients': grad, 'rgb_map': rgb, 'acc_map': acc,
                 'depth_map': depth, 'msk_sdf': msk_sdf, 'msk_label': msk_label}
-
-    def knn_records(self):
-        """(R*64, 8) uint32 view of the last render's KNN records (anr_sdf_render_knn): w0..w4 float
-        bits, then the five vertex indices packed as i0 | i1 << 16, i2 | i3 << 16, i4 (tests, debugging)."""
-        R = self._last_R
-        addr = self.lib.anr_sdf_render_knn(_lib.ptr(self._ws), R, ctypes.byref(self._last_opts))
-        if not addr:
-            raise RuntimeError('anr_sdf_render_knn: no records')
-        off = addr - self._ws.data_ptr()
-        return self._ws[off:off + R * 64 * 32].view(torch.int32).view(R * 64, 8)
 
     # ---- Network.forward over free samples (anisdf_pdf_network.py:156-224) ------------------------
     def _net_frame(self, batch):
         """SdfFrame of one Network.forward call (no rays): the frame tensors, tbounds as a private copy
         (the call widens batch['tbounds'] in place; a backward re-run needs the bounds it started from)."""
         dev = self.device()
-        fr = {k: _f32(batch[k], dev) for k in FRAME_KEYS}
-        fr['tbounds'] = fr['tbounds'].clone()
-        li = batch['latent_index'].to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
         f = _lib.SdfFrame()
-        for k in FRAME_KEYS:
-            setattr(f, k, fr[k].data_ptr())
-        f.n_verts = fr['pvertices'].shape[-2]
-        f.latent_index, f.occupancy = li.data_ptr(), None
+        fr = self.fill_frame(f, batch, FRAME_KEYS, dev)
+        li = fr.pop('latent_index')
+        fr['tbounds'] = fr['tbounds'].clone()
+        f.tbounds, f.occupancy = fr['tbounds'].data_ptr(), None
         o = _lib.RenderOpts()
         o.n_samples, o.chunk, o.norm_th, o.train_th = int(self.cfg.N_samples), 1, NORM_TH, 0.0
         o.t_rand, o.novel_pose = None, 0
@@ -228,9 +173,7 @@ class Renderer:
             sdf = torch.empty((1, n, 1), device=dev)
             tb_out = torch.empty((2, 3), device=dev)
             ws_bytes = self.lib.anr_sdf_network_workspace_bytes(n, ctypes.byref(c['opts']))
-            if self._ws is None or self._ws.numel() < ws_bytes or self._ws.device != dev:
-                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            ws = self._ws
+            ws = self.workspace(ws_bytes, dev)
             st = _lib.stream_ptr(dev)
             _lib.check(self.lib.anr_sdf_network_fwd(ctypes.byref(p), ctypes.byref(c['frame']), ctypes.byref(x),
                                                     ctypes.byref(c['opts']), _lib.ptr(raw), _lib.ptr(sdf), _lib.ptr(tb_out),
