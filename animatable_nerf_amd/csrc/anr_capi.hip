@@ -45,9 +45,30 @@ int num_cus() {
 
 namespace {
 
-bool mlp_attr_set = false;
-bool mlp_img_attr_set = false;
-bool mlp_ns_attr_set = false;
+// The fused programs: function, dynamic LDS bytes, and whether the LDS attribute has been set (process-wide,
+// on the program's first launch). The render programs by [image][precision: fp32, bf16x3, bf16x6], in the two
+// kernel signatures (64 samples; N_samples = 64 * nseg), and the density programs of anr_alpha_points.
+template <class... X>
+struct Fused {
+  void (*fn)(MlpArgs, X...);
+  const char* name;
+  int lds;
+  bool attr_set;
+};
+constexpr int kLds32 = mlp_lds_bytes<false>(), kLds16 = mlp_lds_bytes<true>();
+Fused<> g_mlp[2][3] = {
+    {{k_mlp, "k_mlp", kLds32, false}, {k_mlp_b16, "k_mlp", kLds16, false}, {k_mlp_x6, "k_mlp", kLds16, false}},
+    {{k_mlp_img, "k_mlp_img", kLds32, false}, {k_mlp_img_b16, "k_mlp_img", kLds16, false},
+     {k_mlp_img_x6, "k_mlp_img", kLds16, false}}};
+Fused<int> g_mlp_ns[2][3] = {
+    {{k_mlp_ns, "k_mlp_ns", kLds32, false}, {k_mlp_b16_ns, "k_mlp_ns", kLds16, false},
+     {k_mlp_x6_ns, "k_mlp_ns", kLds16, false}},
+    {{k_mlp_img_ns, "k_mlp_ns", kLds32, false}, {k_mlp_img_b16_ns, "k_mlp_ns", kLds16, false},
+     {k_mlp_img_x6_ns, "k_mlp_ns", kLds16, false}}};
+Fused<> g_alpha[3] = {{k_alpha, "k_alpha", kLds32, false}, {k_alpha_b16, "k_alpha", kLds16, false},
+                      {k_alpha_x6, "k_alpha", kLds16, false}};
+
+int precision_index(int precision) { return precision == ANR_BF16X6 ? 2 : precision == ANR_BF16X3 ? 1 : 0; }
 
 // measurement: event pairs around the fused network launches (anr_profile_enable / anr_profile_read),
 // and each launch's per-workgroup clock stamps (MlpArgs::clk) in a device arena of kProfSlots slots
@@ -92,7 +113,6 @@ int prof_end(ProfSlot* q, hipStream_t s) {
   return ANR_OK;
 }
 
-// A2-A6 + per-frame prep: memsets, volumes/folds, front-end, ordered compaction (counts[0] = n')
 int RaySplit::run(void* buf, int count, int op, hipStream_t s) const {
   if (!reduce) return ANR_OK;
   if (check_launch("before the ray-split reduction") != ANR_OK) return ANR_E_HIP;
@@ -100,36 +120,77 @@ int RaySplit::run(void* buf, int count, int op, hipStream_t s) const {
   return ANR_OK;
 }
 
-int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
-                   const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x, const RaySplit* split, bool image, int nseg) {
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = image ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const int nch = (R + o->chunk - 1) / o->chunk;
-  int* counts = (int*)(ws + L.counts);
-
+PrepArgs prep_args(const VolCall& c) {
+  const anr_params* p = c.p;
+  const anr_frame* f = c.f;
   PrepArgs pa{};
-  if (image) {
-    // an image workspace has no chunk_max for k_prep's block 0 to reset: counts (entry 1 stays 0) and
-    // chunk_min by memset, as anr_alpha_points does, and k_prep converts no T-pose volume (nt = 0)
-    if (hipMemsetAsync(counts, 0, 16, s) != hipSuccess ||
-        hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess)
-      return fail(ANR_E_HIP, "hipMemsetAsync failed");
-    pa.pbw = f->pbw;
-    pa.pbw32 = (float*)(ws + L.pbw32);
-  } else {
-    pa.counts = counts;  // counts, chunk_min and chunk_max reset by k_prep's block 0
-    pa.chunk_min = (uint64_t*)(ws + L.chunk_min);
-    pa.chunk_max = (uint64_t*)(ws + L.chunk_max);
-    pa.nch = nch;
-    pa.pbw = f->pbw; pa.tbw = f->tbw;
-    pa.pbw32 = (float*)(ws + L.pbw32); pa.tbw32 = (float*)(ws + L.tbw32);
-  }
-  pa.np = (int)np; pa.nt = (int)nt;
+  pa.pbw = f->pbw;
+  pa.pbw32 = (float*)(c.ws + c.L.pbw32);
+  pa.np = (int)((long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2]);
   pa.w_bw0 = p->t[28]; pa.b_bw0 = p->t[29]; pa.w_bw5 = p->t[38]; pa.b_bw5 = p->t[39];
   pa.bw_latent = p->t[27]; pa.w_lat = p->t[21]; pa.b_lat = p->t[22]; pa.nf_latent = p->t[0];
   pa.latent_index = f->latent_index;
-  pa.fold = (float*)(ws + L.fold);
+  pa.fold = (float*)(c.ws + c.L.fold);
+  if (c.o.novel_pose) {
+    pa.novel = 1;
+    pa.n_latent = p->novel[0];
+    pa.nw_bw0 = p->novel[1]; pa.nb_bw0 = p->novel[2];
+    pa.nw_bw5 = p->novel[11]; pa.nb_bw5 = p->novel[12];
+    pa.bw_latent_index = f->bw_latent_index;
+  }
+  return pa;
+}
+
+int compact_rows(const VolCall& c, bool one_launch) {
+  const int R = c.R;
+  int* counts = (int*)(c.ws + c.L.counts);
+  CompactArgs ca{};
+  ca.n_rays = R; ca.chunk = c.o.chunk;
+  ca.ray_offset = c.split ? c.split->ray_offset : 0;
+  ca.mask = (uint64_t*)(c.ws + c.L.mask);
+  ca.chunk_min = (const uint64_t*)(c.ws + c.L.chunk_min);
+  ca.ray_off = (int*)(c.ws + c.L.ray_off);
+  ca.block_sum = (int*)(c.ws + c.L.block_sum);
+  ca.list = (int*)(c.ws + c.L.list);
+  if (one_launch) {
+    hipLaunchKernelGGL(k_compact1, dim3(1), dim3(1024), 0, c.s, ca, counts);
+    return check_launch("k_compact1");
+  }
+  const int nb = (R + 255) / 256;
+  hipLaunchKernelGGL(k_count, dim3(nb), dim3(256), 0, c.s, ca);
+  ANR_TRY(check_launch("k_count"));
+  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, c.s, ca.block_sum, nb, counts);
+  ANR_TRY(check_launch("k_scan_blocks"));
+  hipLaunchKernelGGL(k_compact, dim3((R + 3) / 4), dim3(256), 0, c.s, ca);
+  return check_launch("k_compact");
+}
+
+// A2-A6 + per-frame prep: memsets, volumes/folds, front-end, ordered compaction (counts[0] = n')
+int stage_frontend(const VolCall& c) {
+  const anr_params* p = c.p;
+  const anr_frame* f = c.f;
+  const Layout& L = c.L;
+  char* ws = c.ws;
+  hipStream_t s = c.s;
+  const int R = c.R;
+  const int nch = (R + c.o.chunk - 1) / c.o.chunk;
+
+  PrepArgs pa = prep_args(c);
+  if (c.image) {
+    // an image workspace has no chunk_max for k_prep's block 0 to reset: counts (entry 1 stays 0) and
+    // chunk_min by memset, as anr_alpha_points does, and k_prep converts no T-pose volume (nt = 0)
+    if (hipMemsetAsync(ws + L.counts, 0, 16, s) != hipSuccess ||
+        hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess)
+      return fail(ANR_E_HIP, "hipMemsetAsync failed");
+  } else {
+    pa.counts = (int*)(ws + L.counts);  // counts, chunk_min and chunk_max reset by k_prep's block 0
+    pa.chunk_min = (uint64_t*)(ws + L.chunk_min);
+    pa.chunk_max = (uint64_t*)(ws + L.chunk_max);
+    pa.nch = nch;
+    pa.tbw = f->tbw;
+    pa.tbw32 = (float*)(ws + L.tbw32);
+    pa.nt = (int)((long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2]);
+  }
   pa.pn24 = (float*)(ws + L.pn24);
   if (p->packed) {  // the bf16x3 program's folded head (anr_layers.h ANR_L_HEAD)
     const float* head = (const float*)((const unsigned char*)p->packed + head_base());
@@ -137,41 +198,31 @@ int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, 
     pa.head_q = head + ANR_HEAD_Q_OFF;
     pa.b_alpha = p->t[18];
   }
-  if (o->novel_pose) {
-    pa.novel = 1;
-    pa.n_latent = p->novel[0];
-    pa.nw_bw0 = p->novel[1]; pa.nb_bw0 = p->novel[2];
-    pa.nw_bw5 = p->novel[11]; pa.nb_bw5 = p->novel[12];
-    pa.bw_latent_index = f->bw_latent_index;
-  }
-  hipLaunchKernelGGL(k_prep, dim3(prep_blocks(np, nt)), dim3(256), 0, s, pa);
+  hipLaunchKernelGGL(k_prep, dim3(prep_blocks(pa.np, pa.nt)), dim3(256), 0, s, pa);
   ANR_TRY(check_launch("k_prep"));
 
   FrontArgs fa{};
-  fa.ray_o = ray_o; fa.ray_d = ray_d; fa.near_ = near_; fa.far_ = far_; fa.t_rand = o->t_rand;
-  fa.n_rays = R; fa.chunk = o->chunk;
-  fa.ray_offset = split ? split->ray_offset : 0;
+  fa.ray_o = c.ray_o; fa.ray_d = c.ray_d; fa.near_ = c.near_; fa.far_ = c.far_; fa.t_rand = c.o.t_rand;
+  fa.n_rays = R; fa.chunk = c.o.chunk;
+  fa.ray_offset = c.split ? c.split->ray_offset : 0;
   fa.R = f->R; fa.Th = f->Th; fa.pbw = f->pbw; fa.pbounds = f->pbounds;
   fa.pn24 = pa.pn24;
   fa.X = f->pbw_dims[0]; fa.Y = f->pbw_dims[1]; fa.Z = f->pbw_dims[2];
-  fa.norm_th = o->norm_th;
+  fa.norm_th = c.o.norm_th;
   fa.mask = (uint64_t*)(ws + L.mask);
   fa.chunk_min = (uint64_t*)(ws + L.chunk_min);
-  fa.raw = raw;
+  fa.raw = c.raw;
   fa.n_views = f->n_views;
   fa.Ks = f->Ks; fa.RT = f->RT; fa.msks = f->msks;
   fa.img_h = f->img_h; fa.img_w = f->img_w;
-  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
-    return fail(ANR_E_ARG, "render: bad visibility-filter views");
-  if (x) {  // free samples: world->pose with the matmul path of an n_pts-point call, argmin over the call
-    if (f->n_views) return fail(ANR_E_ARG, "network forward: the visibility filter is a renderer option");
-    fa.wpts = x->wpts;
-    fa.n_pts = x->n_pts;
-    fa.chunk_pts = x->n_pts;
+  if (c.x) {  // free samples: world->pose with the matmul path of an n_pts-point call, argmin over the call
+    fa.wpts = c.x->wpts;
+    fa.n_pts = c.x->n_pts;
+    fa.chunk_pts = c.x->n_pts;
     hipLaunchKernelGGL(k_frontend_pts, dim3((R + 3) / 4), dim3(256), 0, s, fa);
     ANR_TRY(check_launch("k_frontend_pts"));
-  } else if (nseg > 0) {  // R, chunk and ray_offset in rows
-    hipLaunchKernelGGL(k_frontend_ns, dim3((R + 15) / 16), dim3(1024), 0, s, fa, nseg);
+  } else if (c.nseg > 0) {
+    hipLaunchKernelGGL(k_frontend_ns, dim3((R + 15) / 16), dim3(1024), 0, s, fa, c.nseg);
     ANR_TRY(check_launch("k_frontend_ns"));
   } else {
     hipLaunchKernelGGL(k_frontend, dim3((R + 15) / 16), dim3(1024), 0, s, fa);
@@ -179,135 +230,93 @@ int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, 
   }
 
   // ray split: the chunk's argmin over every rank's samples
-  if (split) ANR_TRY(split->run(fa.chunk_min, (R + o->chunk - 1) / o->chunk, ANR_REDUCE_MIN_U64, s));
-  CompactArgs ca{};
-  ca.n_rays = R; ca.chunk = o->chunk;
-  ca.ray_offset = fa.ray_offset;
-  ca.mask = fa.mask; ca.chunk_min = fa.chunk_min;
-  ca.ray_off = (int*)(ws + L.ray_off);
-  ca.block_sum = (int*)(ws + L.block_sum);
-  ca.list = (int*)(ws + L.list);
-  if (R <= 1024) {  // a training batch: one launch
-    hipLaunchKernelGGL(k_compact1, dim3(1), dim3(1024), 0, s, ca, counts);
-    return check_launch("k_compact1");
+  if (c.split) ANR_TRY(c.split->run(fa.chunk_min, nch, ANR_REDUCE_MIN_U64, s));
+  return compact_rows(c, R <= 1024);  // a training batch: one launch
+}
+
+MlpArgs mlp_args(const VolCall& c) {
+  const anr_params* p = c.p;
+  const anr_frame* f = c.f;
+  MlpArgs ma{};
+  ma.wimg = (const unsigned char*)p->packed;
+  ma.bias = (const float*)((const unsigned char*)p->packed + weights_bytes());
+  ma.fold = (const float*)(c.ws + c.L.fold);
+  ma.A = f->A; ma.R = f->R; ma.Th = f->Th;
+  ma.pbw32 = (const float*)(c.ws + c.L.pbw32); ma.pbounds = f->pbounds;
+  ma.pX = f->pbw_dims[0]; ma.pY = f->pbw_dims[1]; ma.pZ = f->pbw_dims[2];
+  ma.list = (const int*)(c.ws + c.L.list); ma.n_kept = (const int*)(c.ws + c.L.counts);
+  if (c.o.novel_pose) {  // the pose pass reads the novel_pose_bw copy of the blend-weight MLP
+    const int pi = precision_index(c.o.precision);
+    ma.pose_woff = pi == 2 || (pi == 1 && ANR_POSE_MODE == 2) ? ANR_X6_NOVEL_WOFF : pi == 1 ? ANR_B16_NOVEL_WOFF : ANR_NOVEL_WOFF;
+    ma.pose_boff = ANR_NOVEL_BOFF;
   }
-  const int nb = (R + 255) / 256;
-  hipLaunchKernelGGL(k_count, dim3(nb), dim3(256), 0, s, ca);
-  ANR_TRY(check_launch("k_count"));
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, ca.block_sum, nb, counts);
-  ANR_TRY(check_launch("k_scan_blocks"));
-  hipLaunchKernelGGL(k_compact, dim3((R + 3) / 4), dim3(256), 0, s, ca);
-  return check_launch("k_compact");
+  return ma;
+}
+
+// Launch of one fused program over `tiles` 128-sample tiles: its LDS attribute on its first launch, then the
+// launch between the profiling events (profiled: the render programs; prof_begin is a no-op with profiling off)
+template <class... X>
+static int launch_fused(Fused<X...>& k, bool profiled, long tiles, hipStream_t s, MlpArgs& ma, X... extra) {
+  if (!k.attr_set) {
+    if (hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds) != hipSuccess)
+      return fail(ANR_E_HIP, std::string("hipFuncSetAttribute(") + k.name + ") failed");
+    k.attr_set = true;
+  }
+  const int grid = (int)(tiles < num_cus() ? tiles : num_cus());
+  ProfSlot* ps = profiled ? prof_begin(s, grid) : nullptr;
+  ma.clk = ps ? ps->clk : nullptr;
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(512), k.lds, s, ma, extra...);
+  ANR_TRY(check_launch(k.name));
+  return prof_end(ps, s);
+}
+
+int launch_alpha_program(const VolCall& c, MlpArgs& ma, long tiles) {
+  return launch_fused(g_alpha[precision_index(c.o.precision)], false, tiles, c.s, ma);
 }
 
 // the fused network kernel (render path)
-int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
-              const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x, bool image, int nseg) {
-  const long N = (long)R * 64;
-  MlpArgs ma{};
-  if (x) {
-    ma.wpts = x->wpts; ma.vdir = x->viewdir; ma.dists = x->dists;
-    ma.n_pts = x->n_pts; ma.chunk_pts = x->n_pts;
+int stage_mlp(const VolCall& c) {
+  const anr_frame* f = c.f;
+  const Layout& L = c.L;
+  char* ws = c.ws;
+  MlpArgs ma = mlp_args(c);
+  if (c.x) {
+    ma.wpts = c.x->wpts; ma.vdir = c.x->viewdir; ma.dists = c.x->dists;
+    ma.n_pts = c.x->n_pts; ma.chunk_pts = c.x->n_pts;
   }
-  ma.wimg = (const unsigned char*)p->packed;
-  ma.bias = (const float*)((const unsigned char*)p->packed + weights_bytes());
-  ma.fold = (const float*)(ws + L.fold);
-  ma.A = f->A; ma.R = f->R; ma.Th = f->Th;
-  ma.pbw32 = (const float*)(ws + L.pbw32); ma.pbounds = f->pbounds;
   ma.tbounds = f->tbounds;
-  ma.pX = f->pbw_dims[0]; ma.pY = f->pbw_dims[1]; ma.pZ = f->pbw_dims[2];
-  if (!image) {
+  ma.ray_o = c.ray_o; ma.ray_d = c.ray_d; ma.near_ = c.near_; ma.far_ = c.far_; ma.t_rand = c.o.t_rand;
+  ma.raw = c.raw;
+  if (!c.image) {  // the image program writes raw alone
     ma.tbw32 = (const float*)(ws + L.tbw32);
     ma.tX = f->tbw_dims[0]; ma.tY = f->tbw_dims[1]; ma.tZ = f->tbw_dims[2];
-  }
-  ma.ray_o = ray_o; ma.ray_d = ray_d; ma.near_ = near_; ma.far_ = far_; ma.t_rand = o->t_rand;
-  ma.list = (const int*)(ws + L.list); ma.n_kept = (const int*)(ws + L.counts);
-  ma.raw = raw;
-  if (!image) {  // the image program writes raw alone
     ma.sigma = (float*)(ws + L.sigma);
     ma.pbw_rows = (float*)(ws + L.pbw_rows);
     ma.tbw_rows = (float*)(ws + L.tbw_rows);
   }
-  const bool x6 = o->precision == ANR_BF16X6;
-  const bool b16 = o->precision == ANR_BF16X3 || x6;
-  ma.pose_woff = o->novel_pose ? (x6 || (b16 && ANR_POSE_MODE == 2) ? ANR_X6_NOVEL_WOFF : b16 ? ANR_B16_NOVEL_WOFF : ANR_NOVEL_WOFF) : 0;
-  ma.pose_boff = o->novel_pose ? ANR_NOVEL_BOFF : 0;
-  const int lds = b16 ? mlp_lds_bytes<true>() : mlp_lds_bytes<false>();
-  if (!mlp_attr_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<false>()) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)k_mlp_b16, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<true>()) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)k_mlp_x6, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<true>()) !=
-            hipSuccess)
-      return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp) failed");
-    mlp_attr_set = true;
-  }
-  if (image && !mlp_img_attr_set) {
-    if (hipFuncSetAttribute((const void*)k_mlp_img, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            mlp_lds_bytes<false>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_mlp_img_b16, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            mlp_lds_bytes<true>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_mlp_img_x6, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            mlp_lds_bytes<true>()) != hipSuccess)
-      return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_img) failed");
-    mlp_img_attr_set = true;
-  }
-  if (nseg > 0 && !mlp_ns_attr_set) {
-    const void* k32[2] = {(const void*)k_mlp_ns, (const void*)k_mlp_img_ns};
-    const void* k16[4] = {(const void*)k_mlp_b16_ns, (const void*)k_mlp_x6_ns, (const void*)k_mlp_img_b16_ns,
-                          (const void*)k_mlp_img_x6_ns};
-    for (const void* k : k32)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<false>()) != hipSuccess)
-        return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_ns) failed");
-    for (const void* k : k16)
-      if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<true>()) != hipSuccess)
-        return fail(ANR_E_HIP, "hipFuncSetAttribute(k_mlp_ns) failed");
-    mlp_ns_attr_set = true;
-  }
-  const long max_tiles = (N + 127) / 128;
-  const int grid = (int)(max_tiles < num_cus() ? max_tiles : num_cus());
-  ProfSlot* ps = prof_begin(s, grid);
-  ma.clk = ps ? ps->clk : nullptr;
-  if (nseg > 0) {  // N_samples = 64 * nseg: the programs with the general id decode
-    if (image) {
-      if (x6) hipLaunchKernelGGL(k_mlp_img_x6_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-      else if (b16) hipLaunchKernelGGL(k_mlp_img_b16_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-      else hipLaunchKernelGGL(k_mlp_img_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-    } else {
-      if (x6) hipLaunchKernelGGL(k_mlp_x6_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-      else if (b16) hipLaunchKernelGGL(k_mlp_b16_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-      else hipLaunchKernelGGL(k_mlp_ns, dim3(grid), dim3(512), lds, s, ma, nseg);
-    }
-    ANR_TRY(check_launch("k_mlp_ns"));
-    return prof_end(ps, s);
-  }
-  if (image) {
-    if (x6) hipLaunchKernelGGL(k_mlp_img_x6, dim3(grid), dim3(512), lds, s, ma);
-    else if (b16) hipLaunchKernelGGL(k_mlp_img_b16, dim3(grid), dim3(512), lds, s, ma);
-    else hipLaunchKernelGGL(k_mlp_img, dim3(grid), dim3(512), lds, s, ma);
-    ANR_TRY(check_launch("k_mlp_img"));
-    return prof_end(ps, s);
-  }
-  if (x6) hipLaunchKernelGGL(k_mlp_x6, dim3(grid), dim3(512), lds, s, ma);
-  else if (b16) hipLaunchKernelGGL(k_mlp_b16, dim3(grid), dim3(512), lds, s, ma);
-  else hipLaunchKernelGGL(k_mlp, dim3(grid), dim3(512), lds, s, ma);
-  ANR_TRY(check_launch("k_mlp"));
-  return prof_end(ps, s);
+  const long tiles = ((long)c.R * 64 + 127) / 128;
+  const int pi = precision_index(c.o.precision);
+  if (c.nseg > 0)  // N_samples = 64 * nseg: the programs with the general id decode
+    return launch_fused(g_mlp_ns[c.image][pi], true, tiles, c.s, ma, c.nseg);
+  return launch_fused(g_mlp[c.image][pi], true, tiles, c.s, ma);
 }
 
 // A11 alpha_ind rows: sigma' > train_th plus per-chunk argmax (counts[1] = m)
-int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, hipStream_t s, const RaySplit* split) {
+int stage_alpha_ind(const VolCall& c) {
+  const Layout& L = c.L;
+  char* ws = c.ws;
+  hipStream_t s = c.s;
+  const int R = c.R;
+  const RaySplit* split = c.split;
   const long N = (long)R * 64;
-  const int nch = (R + o->chunk - 1) / o->chunk;
+  const int nch = (R + c.o.chunk - 1) / c.o.chunk;
   int* counts = (int*)(ws + L.counts);
   AlphaArgs aa{};
-  aa.n_rays = R; aa.chunk = o->chunk;
+  aa.n_rays = R; aa.chunk = c.o.chunk;
   aa.ray_off = (const int*)(ws + L.ray_off); aa.n_kept = counts;
   aa.sigma = (const float*)(ws + L.sigma);
   aa.chunk_max = (uint64_t*)(ws + L.chunk_max);
-  aa.train_th = o->train_th;
+  aa.train_th = c.o.train_th;
   aa.flags = (uint8_t*)(ws + L.flags);
   aa.block_sum = (int*)(ws + L.block_sum2);
   aa.out_row = (int*)(ws + L.out_row);
@@ -335,17 +344,67 @@ int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, 
 }
 
 // A12 compositing
-int stage_composite(const float* near_, const float* far_, int R, const anr_render_opts* o, const float4* raw,
-                    const anr_render_out* out, float* weights, hipStream_t s, int nseg) {
+int stage_composite(const VolCall& c, int n_rays, const anr_render_out* out) {
   CompositeArgs co{};
-  co.raw = raw; co.near_ = near_; co.far_ = far_; co.t_rand = o->t_rand; co.n_rays = R;
-  co.rgb = out->rgb_map; co.acc = out->acc_map; co.depth = out->depth_map; co.weights = weights;
-  if (nseg > 0) {
-    hipLaunchKernelGGL(k_composite_ns, dim3((R + 3) / 4), dim3(256), 0, s, co, nseg);
+  co.raw = c.raw; co.near_ = c.near_; co.far_ = c.far_; co.t_rand = c.o.t_rand; co.n_rays = n_rays;
+  co.rgb = out->rgb_map; co.acc = out->acc_map; co.depth = out->depth_map;
+  if (c.nseg > 0) {
+    hipLaunchKernelGGL(k_composite_ns, dim3((n_rays + 3) / 4), dim3(256), 0, c.s, co, c.nseg);
     return check_launch("k_composite_ns");
   }
-  hipLaunchKernelGGL(k_composite, dim3((R + 3) / 4), dim3(256), 0, s, co);
+  hipLaunchKernelGGL(k_composite, dim3((n_rays + 3) / 4), dim3(256), 0, c.s, co);
   return check_launch("k_composite");
+}
+
+// ---- argument checks of the blend-volume entries -----------------------------------------------------
+int check_novel(const std::string& w, const anr_params* p, const anr_frame* f) {
+  for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
+    if (!p->novel[i]) return fail(ANR_E_ARG, w + ": novel_pose needs the novel_pose_bw tensors");
+  if (!f->bw_latent_index) return fail(ANR_E_ARG, w + ": novel_pose needs bw_latent_index");
+  return ANR_OK;
+}
+
+int check_views(const std::string& w, const anr_frame* f) {
+  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
+    return fail(ANR_E_ARG, w + ": bad visibility-filter views");
+  return ANR_OK;
+}
+
+static int ns_segments(int n_samples) {
+  return (n_samples == 64 || n_samples == 128 || n_samples == 192 || n_samples == 256) ? n_samples / 64 : 0;
+}
+
+int check_vol_call(const VolCheck& k, const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                   const float* near_, const float* far_, int n_rays, const anr_render_opts* o, const anr_render_out* out,
+                   const anr_samples* x, const float* raw, const void* ws) {
+  const std::string w(k.who);
+  if (!p || !f || !o || !ws || (k.samples ? !x : !out)) return fail(ANR_E_ARG, w + ": NULL argument");
+  if (k.samples) {
+    if (!x->wpts || !x->viewdir || !x->dists) return fail(ANR_E_ARG, w + ": NULL sample tensor");
+    if (x->n_pts <= 0 || (long)x->n_pts > 0x7fffffffL / 24 - 64) return fail(ANR_E_ARG, w + ": bad n_pts");
+  } else {
+    if (k.ns ? ns_segments(o->n_samples) == 0 : o->n_samples != 64)
+      return fail(ANR_E_ARG, w + (k.ns ? ": N_samples must be 64, 128, 192 or 256" : ": only N_samples == 64 is supported"));
+    if (o->chunk <= 0) return fail(ANR_E_ARG, w + ": chunk must be > 0");
+    if (n_rays <= 0) return fail(ANR_E_ARG, w + ": n_rays must be > 0");
+    if ((long)n_rays * o->n_samples > 0x7fffffffL / 24)
+      return fail(ANR_E_ARG, w + ": too many rays for one call" +
+                                 (k.ns ? " (24 n_rays N_samples must stay below 2^31)" : ""));
+    if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
+      return fail(ANR_E_ARG, w + ": NULL tensor");
+  }
+  for (int i = 0; i < 3; ++i)
+    if (f->pbw_dims[i] <= 0 || (k.tbw && f->tbw_dims[i] <= 0)) return fail(ANR_E_ARG, w + ": bad volume dims");
+  if (!f->A || !f->R || !f->Th || !f->pbw || (k.tbw && !f->tbw) || !f->pbounds || !f->tbounds || !f->latent_index)
+    return fail(ANR_E_ARG, w + ": NULL frame tensor");
+  if (k.samples) {
+    if (f->n_views) return fail(ANR_E_ARG, w + ": the visibility filter is a renderer option (n_views must be 0)");
+    for (int i = 0; i < ANR_NUM_TENSORS; ++i)
+      if (!p->t[i]) return fail(ANR_E_ARG, w + ": NULL parameter tensor");
+    if (!raw || !p->packed) return fail(ANR_E_ARG, w + ": NULL raw / weights not packed");
+  }
+  if (o->novel_pose) ANR_TRY(check_novel(w, p, f));
+  return k.samples ? ANR_OK : check_views(w, f);
 }
 
 }  // namespace anr
@@ -366,6 +425,15 @@ int anr_near_far(const float* ray_o, const float* ray_d, int n, const float* bou
   return check_launch("k_near_far");
 }
 
+// the camera of the three ray entries (anr_camera_rays, anr_train_ray_gather, anr_train_ray_sample)
+static void fill_cam(CamArgs& a, int H, int W, const double* Kinv, const double* R, const double* T, const double* origin,
+                     int fp64, const float* bounds) {
+  a.H = H; a.W = W; a.fp64 = fp64 ? 1 : 0;
+  for (int k = 0; k < 9; ++k) { a.Kinv[k] = Kinv[k]; a.R[k] = R[k]; }
+  for (int k = 0; k < 3; ++k) { a.T[k] = T[k]; a.o[k] = origin[k]; }
+  a.bounds = bounds;
+}
+
 size_t anr_camera_rays_workspace_bytes(int H, int W) {
   if (H <= 0 || W <= 0) return 0;
   const size_t P = (size_t)H * W;
@@ -383,10 +451,7 @@ int anr_camera_rays(int H, int W, const double* Kinv, const double* R, const dou
   const size_t P = (size_t)H * W;
   char* ws = (char*)workspace;
   CamArgs a{};
-  a.H = H; a.W = W; a.fp64 = fp64 ? 1 : 0;
-  for (int k = 0; k < 9; ++k) { a.Kinv[k] = Kinv[k]; a.R[k] = R[k]; }
-  for (int k = 0; k < 3; ++k) { a.T[k] = T[k]; a.o[k] = origin[k]; }
-  a.bounds = bounds;
+  fill_cam(a, H, W, Kinv, R, T, origin, fp64, bounds);
   a.all_o = (float*)ws;
   a.all_d = (float*)(ws + align256(P * 12));
   a.all_near = (float*)(ws + 2 * align256(P * 12));
@@ -441,10 +506,7 @@ int anr_train_ray_gather(int H, int W, const double* Kinv, const double* R, cons
   if (n > (1L << 24)) return fail(ANR_E_ARG, "anr_train_ray_gather: too many draws");
   if (n == 0) return ANR_OK;
   TrainRayArgs a{};
-  a.cam.H = H; a.cam.W = W; a.cam.fp64 = fp64 ? 1 : 0;
-  for (int k = 0; k < 9; ++k) { a.cam.Kinv[k] = Kinv[k]; a.cam.R[k] = R[k]; }
-  for (int k = 0; k < 3; ++k) { a.cam.T[k] = T[k]; a.cam.o[k] = origin[k]; }
-  a.cam.bounds = bounds;
+  fill_cam(a.cam, H, W, Kinv, R, T, origin, fp64, bounds);
   a.img = img; a.bound_mask = bound_mask; a.mask_bkgd = mask_bkgd ? 1 : 0;
   a.lists = const_cast<int*>(lists); a.draws = draws;
   a.n_seg[0] = n_body; a.n_seg[1] = n_face; a.n_seg[2] = n_rand;
@@ -479,10 +541,7 @@ int anr_train_ray_sample(int H, int W, const double* Kinv, const double* R, cons
     return fail(ANR_E_ARG, "anr_train_ray_sample: NULL pixel list");
   TrainSampleArgs s{};
   TrainRayArgs& a = s.r;
-  a.cam.H = H; a.cam.W = W; a.cam.fp64 = fp64 ? 1 : 0;
-  for (int k = 0; k < 9; ++k) { a.cam.Kinv[k] = Kinv[k]; a.cam.R[k] = R[k]; }
-  for (int k = 0; k < 3; ++k) { a.cam.T[k] = T[k]; a.cam.o[k] = origin[k]; }
-  a.cam.bounds = bounds;
+  fill_cam(a.cam, H, W, Kinv, R, T, origin, fp64, bounds);
   a.img = img; a.bound_mask = bound_mask; a.mask_bkgd = mask_bkgd ? 1 : 0;
   a.cap = nrays; a.n_out = n_out;
   a.ray_o = ray_o; a.ray_d = ray_d; a.rgb = rgb; a.near_ = near_; a.far_ = far_; a.coord = coord;
@@ -536,37 +595,54 @@ const int32_t* anr_render_counts(const void* workspace, int n_rays) {
   return (const int32_t*)((const char*)workspace + layout(n_rays, 1, 0, 0, false).counts);
 }
 
+// rows and rows per chunk of an N_samples render as ints: 24 * n_rays * n_samples < 2^31 bounds the rows; the chunk
+// is clamped to the call's rays (a chunk no call can fill behaves like one chunk), so chunk * nseg fits too
+static bool ns_rows(int n_rays, const anr_render_opts* o, int nseg, int* rows, int* chunk_rows) {
+  if (n_rays <= 0 || o->chunk <= 0 || nseg <= 0) return false;
+  if ((long)n_rays * nseg * 64 > 0x7fffffffL / 24) return false;
+  *rows = n_rays * nseg;
+  *chunk_rows = (o->chunk < n_rays ? o->chunk : n_rays) * nseg;
+  return true;
+}
+
+// The three ray renders: check, layout, front-end, program, alpha_ind (not image-only), compositing.
+// ns: anr_render_ns_fwd. A ray is nseg = N_samples / 64 rows of 64 samples: the workspace is layout() /
+// layout_image() of n_rays * nseg rows with chunk * nseg rows per chunk, so every region that scaled with R * 64
+// scales with R * N_samples and the number of chunks is unchanged; the `_ns` kernels run, at 64 samples too.
+// Otherwise the 64-sample kernels over rays.
+static int render_rays(const char* who, bool ns, bool image, const anr_params* p, const anr_frame* f, const float* ray_o,
+                       const float* ray_d, const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
+                       const anr_render_out* out, void* workspace, size_t ws_bytes, void* stream) {
+  ANR_TRY(check_vol_call({who, false, !image, ns}, p, f, ray_o, ray_d, near_, far_, n_rays, o, out, nullptr, nullptr,
+                         workspace));
+  VolCall c{};
+  c.p = p; c.f = f;
+  c.ray_o = ray_o; c.ray_d = ray_d; c.near_ = near_; c.far_ = far_;
+  c.R = n_rays;
+  c.o = *o;
+  c.image = image;
+  if (ns) {  // the stages count in rows
+    c.nseg = o->n_samples / 64;
+    ns_rows(n_rays, o, c.nseg, &c.R, &c.o.chunk);
+  }
+  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
+  const long nt = image ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
+  c.L = image ? layout_image(c.R, c.o.chunk, np, out->raw == nullptr) : layout(c.R, c.o.chunk, np, nt, out->raw == nullptr);
+  if (ws_bytes < c.L.total) return fail(ANR_E_WORKSPACE, std::string(who) + ": workspace too small");
+  c.ws = (char*)workspace;
+  c.raw = out->raw ? (float4*)out->raw : (float4*)(c.ws + c.L.raw);
+  c.s = (hipStream_t)stream;
+  ANR_TRY(stage_frontend(c));
+  ANR_TRY(stage_mlp(c));
+  if (!image) ANR_TRY(stage_alpha_ind(c));
+  return stage_composite(c, n_rays, out);
+}
+
 int anr_render_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
                    const float* far_, int n_rays, const anr_render_opts* o, const anr_render_out* out, void* workspace,
                    size_t ws_bytes, void* stream) {
-  if (!p || !f || !o || !out || !workspace) return fail(ANR_E_ARG, "anr_render_fwd: NULL argument");
-  if (o->n_samples != 64) return fail(ANR_E_ARG, "anr_render_fwd: only N_samples == 64 is supported");
-  if (o->chunk <= 0) return fail(ANR_E_ARG, "anr_render_fwd: chunk must be > 0");
-  if (n_rays <= 0) return fail(ANR_E_ARG, "anr_render_fwd: n_rays must be > 0");
-  if ((long)n_rays * 64 > 0x7fffffffL / 24) return fail(ANR_E_ARG, "anr_render_fwd: too many rays for one call");
-  if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
-    return fail(ANR_E_ARG, "anr_render_fwd: NULL tensor");
-  for (int i = 0; i < 3; ++i)
-    if (f->pbw_dims[i] <= 0 || f->tbw_dims[i] <= 0) return fail(ANR_E_ARG, "anr_render_fwd: bad volume dims");
-  if (!f->A || !f->R || !f->Th || !f->pbw || !f->tbw || !f->pbounds || !f->tbounds || !f->latent_index)
-    return fail(ANR_E_ARG, "anr_render_fwd: NULL frame tensor");
-  if (o->novel_pose) {
-    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_render_fwd: novel_pose needs the novel_pose_bw tensors");
-    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_render_fwd: novel_pose needs bw_latent_index");
-  }
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const Layout L = layout(n_rays, o->chunk, np, nt, out->raw == nullptr);
-  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_render_fwd: workspace too small");
-
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float4* raw = out->raw ? (float4*)out->raw : (float4*)(ws + L.raw);
-  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s));
-  ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s));
-  ANR_TRY(stage_alpha_ind(n_rays, o, ws, L, s));
-  return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s);
+  return render_rays("anr_render_fwd", false, false, p, f, ray_o, ray_d, near_, far_, n_rays, o, out, workspace, ws_bytes,
+                     stream);
 }
 
 // ---- image-only render (include/aninerf.h): front-end -> image program -> compositing ------
@@ -581,53 +657,11 @@ size_t anr_render_image_workspace_bytes(int n_rays, const anr_render_opts* o, co
 int anr_render_image_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
                          const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
                          const anr_render_out* out, void* workspace, size_t ws_bytes, void* stream) {
-  if (!p || !f || !o || !out || !workspace) return fail(ANR_E_ARG, "anr_render_image_fwd: NULL argument");
-  if (o->n_samples != 64) return fail(ANR_E_ARG, "anr_render_image_fwd: only N_samples == 64 is supported");
-  if (o->chunk <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: chunk must be > 0");
-  if (n_rays <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: n_rays must be > 0");
-  if ((long)n_rays * 64 > 0x7fffffffL / 24) return fail(ANR_E_ARG, "anr_render_image_fwd: too many rays for one call");
-  if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
-    return fail(ANR_E_ARG, "anr_render_image_fwd: NULL tensor");
-  for (int i = 0; i < 3; ++i)
-    if (f->pbw_dims[i] <= 0) return fail(ANR_E_ARG, "anr_render_image_fwd: bad volume dims");
-  if (!f->A || !f->R || !f->Th || !f->pbw || !f->pbounds || !f->tbounds || !f->latent_index)
-    return fail(ANR_E_ARG, "anr_render_image_fwd: NULL frame tensor");
-  if (o->novel_pose) {
-    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_render_image_fwd: novel_pose needs the novel_pose_bw tensors");
-    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_render_image_fwd: novel_pose needs bw_latent_index");
-  }
-  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
-    return fail(ANR_E_ARG, "anr_render_image_fwd: bad visibility-filter views");
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const Layout L = layout_image(n_rays, o->chunk, np, out->raw == nullptr);
-  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_render_image_fwd: workspace too small");
-
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float4* raw = out->raw ? (float4*)out->raw : (float4*)(ws + L.raw);
-  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, nullptr, true));
-  ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, n_rays, o, ws, L, raw, s, nullptr, true));
-  return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s);
+  return render_rays("anr_render_image_fwd", false, true, p, f, ray_o, ray_d, near_, far_, n_rays, o, out, workspace,
+                     ws_bytes, stream);
 }
 
 // ---- render at N_samples = 64, 128, 192 or 256 (include/aninerf.h) --------------------------
-// A ray is nseg = N_samples / 64 rows of 64 samples: the workspace is layout() / layout_image() of
-// n_rays * nseg rows with chunk * nseg rows per chunk, so every region that scaled with R * 64 scales
-// with R * N_samples and the number of chunks is unchanged.
-static int ns_segments(int n_samples) {
-  return (n_samples == 64 || n_samples == 128 || n_samples == 192 || n_samples == 256) ? n_samples / 64 : 0;
-}
-// rows and rows per chunk as ints: 24 * n_rays * n_samples < 2^31 bounds the rows; the chunk is clamped to the
-// call's rays (a chunk no call can fill behaves like one chunk), so chunk * nseg fits too
-static bool ns_rows(int n_rays, const anr_render_opts* o, int nseg, int* rows, int* chunk_rows) {
-  if (n_rays <= 0 || o->chunk <= 0 || nseg <= 0) return false;
-  if ((long)n_rays * nseg * 64 > 0x7fffffffL / 24) return false;
-  *rows = n_rays * nseg;
-  *chunk_rows = (o->chunk < n_rays ? o->chunk : n_rays) * nseg;
-  return true;
-}
-
 size_t anr_render_ns_workspace_bytes(int n_rays, const anr_render_opts* o, const anr_frame* f, int image_only) {
   if (!o || !f) return 0;
   int rows, chunk_rows;
@@ -643,44 +677,8 @@ size_t anr_render_ns_workspace_bytes(int n_rays, const anr_render_opts* o, const
 int anr_render_ns_fwd(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
                       const float* near_, const float* far_, int n_rays, const anr_render_opts* o,
                       const anr_render_out* out, int image_only, void* workspace, size_t ws_bytes, void* stream) {
-  if (!p || !f || !o || !out || !workspace) return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL argument");
-  const int nseg = ns_segments(o->n_samples);
-  if (nseg == 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: N_samples must be 64, 128, 192 or 256");
-  if (o->chunk <= 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: chunk must be > 0");
-  if (n_rays <= 0) return fail(ANR_E_ARG, "anr_render_ns_fwd: n_rays must be > 0");
-  int rows, chunk_rows;
-  if (!ns_rows(n_rays, o, nseg, &rows, &chunk_rows))
-    return fail(ANR_E_ARG, "anr_render_ns_fwd: too many rays for one call (24 n_rays N_samples must stay below 2^31)");
-  if (!ray_o || !ray_d || !near_ || !far_ || !out->rgb_map || !out->acc_map || !out->depth_map || !p->packed)
-    return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL tensor");
-  for (int i = 0; i < 3; ++i)
-    if (f->pbw_dims[i] <= 0 || (!image_only && f->tbw_dims[i] <= 0))
-      return fail(ANR_E_ARG, "anr_render_ns_fwd: bad volume dims");
-  if (!f->A || !f->R || !f->Th || !f->pbw || (!image_only && !f->tbw) || !f->pbounds || !f->tbounds || !f->latent_index)
-    return fail(ANR_E_ARG, "anr_render_ns_fwd: NULL frame tensor");
-  if (o->novel_pose) {
-    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_render_ns_fwd: novel_pose needs the novel_pose_bw tensors");
-    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_render_ns_fwd: novel_pose needs bw_latent_index");
-  }
-  if (f->n_views < 0 || (f->n_views > 0 && (!f->Ks || !f->RT || !f->msks || f->img_h <= 0 || f->img_w <= 0)))
-    return fail(ANR_E_ARG, "anr_render_ns_fwd: bad visibility-filter views");
-  const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const long nt = image_only ? 0 : (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const bool img = image_only != 0;
-  const Layout L = img ? layout_image(rows, chunk_rows, np, out->raw == nullptr)
-                       : layout(rows, chunk_rows, np, nt, out->raw == nullptr);
-  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_render_ns_fwd: workspace too small");
-
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float4* raw = out->raw ? (float4*)out->raw : (float4*)(ws + L.raw);
-  anr_render_opts oo = *o;
-  oo.chunk = chunk_rows;  // the stages below count in rows
-  ANR_TRY(stage_frontend(p, f, ray_o, ray_d, near_, far_, rows, &oo, ws, L, raw, s, nullptr, nullptr, img, nseg));
-  ANR_TRY(stage_mlp(p, f, ray_o, ray_d, near_, far_, rows, &oo, ws, L, raw, s, nullptr, img, nseg));
-  if (!img) ANR_TRY(stage_alpha_ind(rows, &oo, ws, L, s));
-  return stage_composite(near_, far_, n_rays, o, raw, out, nullptr, s, nseg);
+  return render_rays("anr_render_ns_fwd", true, image_only != 0, p, f, ray_o, ray_d, near_, far_, n_rays, o, out,
+                     workspace, ws_bytes, stream);
 }
 
 int anr_render_ns_bw_rows(const void* workspace, int n_rays, int n_samples, float* pbw, float* tbw, void* stream) {
@@ -700,22 +698,6 @@ int anr_render_ns_row_ids(const void* workspace, int n_rays, int n_samples, int3
 }
 
 // ---- Network.forward over free samples (include/aninerf.h) --------------------------------
-static int check_network_args(const anr_params* p, const anr_frame* f, const anr_samples* x, const anr_render_opts* o,
-                              const void* ws, const char* who) {
-  const std::string w(who);
-  if (!p || !f || !x || !o || !ws) return fail(ANR_E_ARG, w + ": NULL argument");
-  if (!x->wpts || !x->viewdir || !x->dists) return fail(ANR_E_ARG, w + ": NULL sample tensor");
-  if (x->n_pts <= 0 || (long)x->n_pts > 0x7fffffffL / 24 - 64) return fail(ANR_E_ARG, w + ": bad n_pts");
-  for (int i = 0; i < 3; ++i)
-    if (f->pbw_dims[i] <= 0 || f->tbw_dims[i] <= 0) return fail(ANR_E_ARG, w + ": bad volume dims");
-  if (!f->A || !f->R || !f->Th || !f->pbw || !f->tbw || !f->pbounds || !f->tbounds || !f->latent_index)
-    return fail(ANR_E_ARG, w + ": NULL frame tensor");
-  if (f->n_views) return fail(ANR_E_ARG, w + ": the visibility filter is a renderer option (n_views must be 0)");
-  for (int i = 0; i < ANR_NUM_TENSORS; ++i)
-    if (!p->t[i]) return fail(ANR_E_ARG, w + ": NULL parameter tensor");
-  return ANR_OK;
-}
-
 size_t anr_network_workspace_bytes(int n_pts, const anr_render_opts* o, const anr_frame* f) {
   if (!o || !f || n_pts <= 0) return 0;
   const int G = (n_pts + 63) / 64;
@@ -734,28 +716,26 @@ int anr_network_bw_rows(const void* workspace, int n_pts, float* pbw, float* tbw
 
 int anr_network_fwd(const anr_params* p, const anr_frame* f, const anr_samples* x, const anr_render_opts* o, float* raw,
                     void* workspace, size_t ws_bytes, void* stream) {
-  ANR_TRY(check_network_args(p, f, x, o, workspace, "anr_network_fwd"));
-  if (!raw || !p->packed) return fail(ANR_E_ARG, "anr_network_fwd: NULL raw / weights not packed");
-  if (o->novel_pose) {
-    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_network_fwd: novel_pose needs the novel_pose_bw tensors");
-    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_network_fwd: novel_pose needs bw_latent_index");
-  }
+  ANR_TRY(check_vol_call({"anr_network_fwd", true, true, false}, p, f, nullptr, nullptr, nullptr, nullptr, 0, o, nullptr,
+                         x, raw, workspace));
   const int G = (x->n_pts + 63) / 64;
-  anr_render_opts oo = *o;
-  oo.chunk = G;  // one call = one reference chunk
-  oo.t_rand = nullptr;
+  VolCall c{};
+  c.p = p; c.f = f; c.x = x;
+  c.R = G;
+  c.o = *o;
+  c.o.chunk = G;  // one call = one reference chunk
+  c.o.t_rand = nullptr;
   const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
   const long nt = (long)f->tbw_dims[0] * f->tbw_dims[1] * f->tbw_dims[2];
-  const Layout L = layout(G, G, np, nt, true);
-  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_network_fwd: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  float4* wraw = (float4*)(ws + L.raw);
-  ANR_TRY(stage_frontend(p, f, nullptr, nullptr, nullptr, nullptr, G, &oo, ws, L, wraw, s, x));
-  ANR_TRY(stage_mlp(p, f, nullptr, nullptr, nullptr, nullptr, G, &oo, ws, L, wraw, s, x));
-  ANR_TRY(stage_alpha_ind(G, &oo, ws, L, s));
-  if (hipMemcpyAsync(raw, wraw, (size_t)x->n_pts * 16, hipMemcpyDeviceToDevice, s) != hipSuccess)
+  c.L = layout(G, G, np, nt, true);
+  if (ws_bytes < c.L.total) return fail(ANR_E_WORKSPACE, "anr_network_fwd: workspace too small");
+  c.ws = (char*)workspace;
+  c.raw = (float4*)(c.ws + c.L.raw);
+  c.s = (hipStream_t)stream;
+  ANR_TRY(stage_frontend(c));
+  ANR_TRY(stage_mlp(c));
+  ANR_TRY(stage_alpha_ind(c));
+  if (hipMemcpyAsync(raw, c.raw, (size_t)x->n_pts * 16, hipMemcpyDeviceToDevice, c.s) != hipSuccess)
     return fail(ANR_E_HIP, "anr_network_fwd: raw copy failed");
   return ANR_OK;
 }

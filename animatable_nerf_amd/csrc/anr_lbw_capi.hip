@@ -281,14 +281,16 @@ int anr_lbw_render_fwd(const anr_lbw_params* p, const anr_lbw_frame* f, const fl
     ANR_TRY(check_launch("k_lbw_raw"));
   }
 
+  VolCall v{};  // what stage_alpha_ind and stage_composite read
+  v.near_ = near_; v.far_ = far_; v.R = R; v.o = *o; v.ws = ws; v.raw = raw; v.s = s;
   if (!image) {
-    Layout A{};
+    Layout& A = v.L;
     A.counts = L.F.counts; A.mask = L.F.mask; A.ray_off = L.F.ray_off; A.list = L.F.list; A.sigma = L.sigma;
     A.chunk_max = L.chunk_max; A.flags = L.flags; A.block_sum2 = L.block_sum2; A.out_row = L.out_row;
-    ANR_TRY(stage_alpha_ind(R, o, ws, A, s));
+    ANR_TRY(stage_alpha_ind(v));
   }
   const anr_render_out ro{out->rgb_map, out->acc_map, out->depth_map, out->raw};
-  return stage_composite(near_, far_, R, o, raw, &ro, nullptr, s);
+  return stage_composite(v, R, &ro);
 }
 
 }  // extern "C"

@@ -155,8 +155,6 @@ AlphaLayout alpha_layout(long n_pts, int chunk_pts, long np) {
   return A;
 }
 
-bool alpha_attr_set = false;
-
 struct McLayout {
   size_t flags, cases, voff, toff, vblock, tblock, counts, total;
 };
@@ -217,43 +215,34 @@ int anr_alpha_points(const anr_params* p, const anr_frame* f, const float* wpts,
     if (f->pbw_dims[i] <= 0) return fail(ANR_E_ARG, "anr_alpha_points: bad pbw dims");
   if (!f->A || !f->R || !f->Th || !f->pbw || !f->pbounds || !f->latent_index)
     return fail(ANR_E_ARG, "anr_alpha_points: NULL frame tensor");
-  if (o->novel_pose) {
-    for (int i = 0; i < ANR_NUM_NOVEL_TENSORS; ++i)
-      if (!p->novel[i]) return fail(ANR_E_ARG, "anr_alpha_points: novel_pose needs the novel_pose_bw tensors");
-    if (!f->bw_latent_index) return fail(ANR_E_ARG, "anr_alpha_points: novel_pose needs bw_latent_index");
-  }
+  if (o->novel_pose) ANR_TRY(check_novel("anr_alpha_points", p, f));
+  const int G = (int)((n_pts + 63) / 64);  // groups of 64 points: the rows of the shared stages
+  VolCall c{};
+  c.p = p; c.f = f;
+  c.R = G;
+  c.o.chunk = o->chunk_pts / 64;
+  c.o.norm_th = o->norm_th; c.o.novel_pose = o->novel_pose; c.o.precision = o->precision;
   const long np = (long)f->pbw_dims[0] * f->pbw_dims[1] * f->pbw_dims[2];
-  const Layout L = alpha_layout(n_pts, o->chunk_pts, np).L;
-  if (ws_bytes < L.total) return fail(ANR_E_WORKSPACE, "anr_alpha_points: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = (char*)workspace;
-  const int G = (int)((n_pts + 63) / 64);  // groups of 64 points
-  const int chunk = o->chunk_pts / 64;
-  const int nch = (G + chunk - 1) / chunk;
+  c.L = alpha_layout(n_pts, o->chunk_pts, np).L;
+  if (ws_bytes < c.L.total) return fail(ANR_E_WORKSPACE, "anr_alpha_points: workspace too small");
+  c.ws = (char*)workspace;
+  c.s = (hipStream_t)stream;
+  const Layout& L = c.L;
+  char* ws = c.ws;
+  hipStream_t s = c.s;
+  const int nch = (G + c.o.chunk - 1) / c.o.chunk;
   if (hipMemsetAsync(ws + L.counts, 0, 16, s) != hipSuccess ||
       hipMemsetAsync(ws + L.chunk_min, 0xff, (size_t)nch * 8, s) != hipSuccess ||
       hipMemsetAsync(alpha, 0, (size_t)n_pts * 4, s) != hipSuccess)
     return fail(ANR_E_HIP, "hipMemsetAsync failed");
 
-  // pbw volume repack + the pose-pass folded biases (k_prep with no T-pose volume)
-  PrepArgs pa{};
-  pa.pbw = f->pbw; pa.pbw32 = (float*)(ws + L.pbw32); pa.np = (int)np; pa.nt = 0;
-  pa.w_bw0 = p->t[28]; pa.b_bw0 = p->t[29]; pa.w_bw5 = p->t[38]; pa.b_bw5 = p->t[39];
-  pa.bw_latent = p->t[27]; pa.w_lat = p->t[21]; pa.b_lat = p->t[22]; pa.nf_latent = p->t[0];
-  pa.latent_index = f->latent_index;
-  pa.fold = (float*)(ws + L.fold);
-  if (o->novel_pose) {
-    pa.novel = 1;
-    pa.n_latent = p->novel[0];
-    pa.nw_bw0 = p->novel[1]; pa.nb_bw0 = p->novel[2];
-    pa.nw_bw5 = p->novel[11]; pa.nb_bw5 = p->novel[12];
-    pa.bw_latent_index = f->bw_latent_index;
-  }
+  // pbw volume repack + the pose-pass folded biases (k_prep with no T-pose volume, head or pn24)
+  const PrepArgs pa = prep_args(c);
   hipLaunchKernelGGL(k_prep, dim3(prep_blocks(np, 0)), dim3(256), 0, s, pa);
   ANR_TRY(check_launch("k_prep"));
 
   FrontArgs fa{};
-  fa.n_rays = G; fa.chunk = chunk;
+  fa.n_rays = G; fa.chunk = c.o.chunk;
   fa.R = f->R; fa.Th = f->Th; fa.pbw = f->pbw; fa.pbounds = f->pbounds;
   fa.X = f->pbw_dims[0]; fa.Y = f->pbw_dims[1]; fa.Z = f->pbw_dims[2];
   fa.norm_th = o->norm_th;
@@ -263,50 +252,11 @@ int anr_alpha_points(const anr_params* p, const anr_frame* f, const float* wpts,
   hipLaunchKernelGGL(k_frontend_pts, dim3((G + 3) / 4), dim3(256), 0, s, fa);
   ANR_TRY(check_launch("k_frontend_pts"));
 
-  CompactArgs ca{};
-  ca.n_rays = G; ca.chunk = chunk;
-  ca.mask = fa.mask; ca.chunk_min = fa.chunk_min;
-  ca.ray_off = (int*)(ws + L.ray_off);
-  ca.block_sum = (int*)(ws + L.block_sum);
-  ca.list = (int*)(ws + L.list);
-  const int nb = (G + 255) / 256;
-  hipLaunchKernelGGL(k_count, dim3(nb), dim3(256), 0, s, ca);
-  ANR_TRY(check_launch("k_count"));
-  hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, s, ca.block_sum, nb, (int*)(ws + L.counts));
-  ANR_TRY(check_launch("k_scan_blocks"));
-  hipLaunchKernelGGL(k_compact, dim3((G + 3) / 4), dim3(256), 0, s, ca);
-  ANR_TRY(check_launch("k_compact"));
+  ANR_TRY(compact_rows(c, false));  // always the three launches
 
-  MlpArgs ma{};
-  ma.wimg = (const unsigned char*)p->packed;
-  ma.bias = (const float*)((const unsigned char*)p->packed + weights_bytes());
-  ma.fold = (const float*)(ws + L.fold);
-  ma.A = f->A; ma.R = f->R; ma.Th = f->Th;
-  ma.pbw32 = (const float*)(ws + L.pbw32); ma.pbounds = f->pbounds;
-  ma.pX = f->pbw_dims[0]; ma.pY = f->pbw_dims[1]; ma.pZ = f->pbw_dims[2];
-  ma.list = (const int*)(ws + L.list); ma.n_kept = (const int*)(ws + L.counts);
+  MlpArgs ma = mlp_args(c);
   ma.wpts = wpts; ma.n_pts = n_pts; ma.chunk_pts = o->chunk_pts; ma.alpha_out = alpha;
-  const bool x6 = o->precision == ANR_BF16X6;
-  const bool b16 = o->precision == ANR_BF16X3 || x6;
-  ma.pose_woff = o->novel_pose ? (x6 || (b16 && ANR_POSE_MODE == 2) ? ANR_X6_NOVEL_WOFF : b16 ? ANR_B16_NOVEL_WOFF : ANR_NOVEL_WOFF) : 0;
-  ma.pose_boff = o->novel_pose ? ANR_NOVEL_BOFF : 0;
-  if (!alpha_attr_set) {
-    if (hipFuncSetAttribute((const void*)k_alpha, hipFuncAttributeMaxDynamicSharedMemorySize, mlp_lds_bytes<false>()) !=
-            hipSuccess ||
-        hipFuncSetAttribute((const void*)k_alpha_b16, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            mlp_lds_bytes<true>()) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_alpha_x6, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            mlp_lds_bytes<true>()) != hipSuccess)
-      return fail(ANR_E_HIP, "hipFuncSetAttribute(k_alpha) failed");
-    alpha_attr_set = true;
-  }
-  const long max_tiles = ((long)G * 64 + 127) / 128;
-  const int cus = num_cus();
-  const int grid = (int)(max_tiles < cus ? max_tiles : cus);
-  if (x6) hipLaunchKernelGGL(k_alpha_x6, dim3(grid), dim3(512), mlp_lds_bytes<true>(), s, ma);
-  else if (b16) hipLaunchKernelGGL(k_alpha_b16, dim3(grid), dim3(512), mlp_lds_bytes<true>(), s, ma);
-  else hipLaunchKernelGGL(k_alpha, dim3(grid), dim3(512), mlp_lds_bytes<false>(), s, ma);
-  return check_launch("k_alpha");
+  return launch_alpha_program(c, ma, ((long)G * 64 + 127) / 128);
 }
 
 const int32_t* anr_alpha_counts(const void* workspace) { return (const int32_t*)workspace; }

@@ -210,10 +210,10 @@ int pdf_core(const anr_pdf_params* p, const anr_pdf_frame* f, const float* ray_o
   }
 
   if (wpts) return ANR_OK;
-  anr_render_opts co{};  // stage_composite reads the sample count and the draws
-  co.n_samples = 64; co.chunk = chunk; co.t_rand = t_rand; co.precision = precision;
+  VolCall v{};  // what stage_composite reads
+  v.near_ = near_; v.far_ = far_; v.o.t_rand = t_rand; v.raw = raw; v.s = s;
   const anr_render_out ro{out->rgb_map, out->acc_map, out->depth_map, out->raw};
-  return stage_composite(near_, far_, R, &co, raw, &ro, nullptr, s);
+  return stage_composite(v, R, &ro);
 }
 
 }  // namespace

@@ -349,7 +349,9 @@ int sdf_render_core(const anr_sdf_params* p, const anr_sdf_frame* f, const float
   if (wpts) return ANR_OK;  // a Network.forward call: no compositing, no msk_sdf lists
   // A12 compositing over the full raw, then B7 msk_sdf / msk_label
   const anr_render_out ro{out->rgb_map, out->acc_map, out->depth_map, out->raw};
-  ANR_TRY(stage_composite(near_, far_, R, o, raw, &ro, nullptr, s));
+  VolCall v{};  // what stage_composite reads
+  v.near_ = near_; v.far_ = far_; v.o.t_rand = o->t_rand; v.raw = raw; v.s = s;
+  ANR_TRY(stage_composite(v, R, &ro));
   SdfMskArgs ma{};
   ma.sdf = out->sdf; ma.occ = f->occupancy; ma.n_rays = R; ma.chunk = chunk;
   ma.min_sdf = F(L.min_sdf); ma.flags = (uint8_t*)(ws + L.flags); ma.chunk_cnt = (int*)(ws + L.chunk_cnt);

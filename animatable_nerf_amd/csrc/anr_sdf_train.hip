@@ -1258,7 +1258,9 @@ int sdf_train_core(const TrainCore& C) {
     // compositing, image loss and d rgb_map
     const anr_sdf_render_out* out = C.out;
     const anr_render_out ro{out->rgb_map, out->acc_map, out->depth_map, nullptr};
-    ANR_TRY(stage_composite(near_, far_, R, o, raw, &ro, nullptr, s));
+    VolCall v{};  // what stage_composite reads
+    v.near_ = near_; v.far_ = far_; v.o.t_rand = o->t_rand; v.raw = raw; v.s = s;
+    ANR_TRY(stage_composite(v, R, &ro));
     TrainBufs tb{};
     tb.raw = raw; tb.draw = (float4*)F(L.draw); tb.n_rays = R; tb.rgb_map = out->rgb_map; tb.d_rgb_map = F(L.drgb);
     tb.n_kept = counts;

@@ -120,7 +120,7 @@ int check_args(const anr_params* p, const anr_frame* f, const float* ray_o, cons
     if (!p->t[i]) return fail(ANR_E_ARG, "train: NULL parameter tensor");
   if (!f->A || !f->R || !f->Th || !f->pbw || !f->tbw || !f->pbounds || !f->tbounds || !f->latent_index)
     return fail(ANR_E_ARG, "train: NULL frame tensor");
-  return ANR_OK;
+  return check_views("train", f);
 }
 
 // ---- side streams -------------------------------------------------------------------------------
@@ -994,7 +994,13 @@ int train_forward(const TrainCall& c, const anr_render_out* out, hipStream_t s, 
       e.bimg = true;
     }
   }
-  ANR_TRY(stage_frontend(p, c.f, c.ray_o, c.ray_d, c.near_, c.far_, R, &c.o, ws, T.L, raw, s, c.x, split));
+  VolCall v{};  // the render stages' view of this call
+  v.p = p; v.f = c.f; v.x = c.x;
+  v.ray_o = c.ray_o; v.ray_d = c.ray_d; v.near_ = c.near_; v.far_ = c.far_;
+  v.R = R; v.o = c.o;
+  v.ws = ws; v.L = T.L; v.raw = raw; v.s = s;
+  v.split = split;
+  ANR_TRY(stage_frontend(v));
   const long N = (long)R * 64;
   e.n_dev = (const int*)(ws + T.L.counts);
   e.cap = (int)N;
@@ -1085,10 +1091,10 @@ int train_forward(const TrainCall& c, const anr_render_out* out, hipStream_t s, 
     hipLaunchKernelGGL(k_tr_raw, dim3(g1), dim3(256), 0, s, b);
     ANR_TRY(check_launch("k_tr_raw"));
   }
-  ANR_TRY(stage_alpha_ind(R, &c.o, ws, T.L, s, split));
+  ANR_TRY(stage_alpha_ind(v));
   ANR_TRY(order(e.ss, s, s2));  // join: the tbw rows
   if (c.x) return ANR_OK;
-  return stage_composite(c.near_, c.far_, R, &c.o, raw, out, nullptr, s);
+  return stage_composite(v, R, out);
 }
 
 // c.x != NULL: free samples; the upstream gradient is d raw (x->n_pts, 4) (NULL: zero) instead of d rgb_map

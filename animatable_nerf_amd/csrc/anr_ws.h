@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/aninerf.h"
+#include "anr_kernels.h"
 #include "anr_layers.h"
 
 namespace anr {
@@ -97,23 +98,63 @@ struct RaySplit {
   int run(void* buf, int count, int op, hipStream_t s) const;
 };
 
-// image: the image-only render on a layout_image() workspace (no T-pose volume, rows or alpha_ind state)
-// x != NULL: free samples (Network.forward): R = ceil(n_pts / 64) groups of 64 samples, the caller's
-// opts with chunk = R (the whole call is one reference chunk) and no t_rand; ray pointers unused
-// nseg > 0 (anr_render_ns_fwd): N_samples = 64 * nseg. R, o->chunk and the layout are then in rows (a ray is
-// nseg rows of 64 samples: R = n_rays * nseg, chunk = rays per chunk * nseg) for stage_frontend, stage_mlp and
-// stage_alpha_ind, whose compaction and alpha_ind kernels run over rows as over rays; stage_composite takes rays.
-// nseg == 0: the 64-sample kernels.
-int stage_frontend(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
-                   const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-                   hipStream_t s, const anr_samples* x = nullptr, const RaySplit* split = nullptr, bool image = false,
-                   int nseg = 0);
-int stage_mlp(const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d, const float* near_,
-              const float* far_, int R, const anr_render_opts* o, char* ws, const Layout& L, float4* raw,
-              hipStream_t s, const anr_samples* x = nullptr, bool image = false, int nseg = 0);
-int stage_alpha_ind(int R, const anr_render_opts* o, char* ws, const Layout& L, hipStream_t s,
-                    const RaySplit* split = nullptr);
-int stage_composite(const float* near_, const float* far_, int R, const anr_render_opts* o, const float4* raw,
-                    const anr_render_out* out, float* weights, hipStream_t s, int nseg = 0);
+// One call of the blend-volume path, filled once per entry and read by every stage. It owns nothing: every
+// pointer is the caller's, nothing is allocated, and the stages only enqueue on `s`.
+//   R, o.chunk, L  in rows. A row is 64 samples: a ray (nseg == 0, the 64-sample kernels), one of the nseg
+//                  rows of a ray (nseg > 0, anr_render_ns_fwd: N_samples = 64 * nseg, the `_ns` kernels, also
+//                  at nseg == 1), or a group of 64 free samples (x, Network.forward: o.chunk = R, the whole
+//                  call is one reference chunk, no t_rand, ray pointers unused). The compaction and alpha_ind
+//                  kernels run over rows as over rays.
+//   image          the image-only render on a layout_image() workspace (no T-pose volume, rows or alpha_ind
+//                  state); anr_alpha_points' workspace (alpha_layout) has the same front-end fields
+//   split          ray split of the reference chunk over ranks (training), or NULL
+// A caller of stage_alpha_ind or stage_composite alone (the KNN-skinned renders) fills what that stage reads.
+struct VolCall {
+  const anr_params* p;
+  const anr_frame* f;
+  const float *ray_o, *ray_d, *near_, *far_;
+  int R;
+  anr_render_opts o;
+  char* ws;
+  Layout L;
+  float4* raw;
+  hipStream_t s;
+  const anr_samples* x;
+  const RaySplit* split;
+  bool image;
+  int nseg;
+};
+
+// ---- argument checks of the blend-volume entries (anr_capi.hip) ----
+// what an entry needs checked; `who` prefixes every message
+struct VolCheck {
+  const char* who;
+  bool samples;  // free samples x and the caller's raw (anr_network_fwd); else rays, outputs, chunk, N_samples
+  bool tbw;      // the T-pose volume (not the image-only renders)
+  bool ns;       // N_samples 64, 128, 192 or 256 (anr_render_ns_fwd); else 64 alone
+};
+int check_vol_call(const VolCheck& k, const anr_params* p, const anr_frame* f, const float* ray_o, const float* ray_d,
+                   const float* near_, const float* far_, int n_rays, const anr_render_opts* o, const anr_render_out* out,
+                   const anr_samples* x, const float* raw, const void* ws);
+int check_novel(const std::string& who, const anr_params* p, const anr_frame* f);  // o->novel_pose: its tensors
+int check_views(const std::string& who, const anr_frame* f);  // the visibility filter's views (n_views == 0: off)
+
+// ---- stages (anr_capi.hip) ----
+// parts of stage_frontend and stage_mlp that anr_alpha_points (anr_mesh.hip) runs with its own front-end launch:
+// k_prep's arguments for the pose volume, the folded biases and the novel-pose tensors; the ordered compaction
+// (one_launch: k_compact1, for R <= 1024; else k_count, k_scan_blocks, k_compact); the fused programs' arguments
+// that every program reads (weights, folds, transforms, pose volume, kept list, pose-pass offsets)
+PrepArgs prep_args(const VolCall& c);
+int compact_rows(const VolCall& c, bool one_launch);
+MlpArgs mlp_args(const VolCall& c);
+// launch of one fused program: grid min(tiles, num_cus()), 512 threads, the program's LDS bytes; its
+// dynamic-LDS attribute is set before its first launch in the process
+int launch_alpha_program(const VolCall& c, MlpArgs& ma, long tiles);  // k_alpha* by c.o.precision
+
+int stage_frontend(const VolCall& c);   // k_prep, front-end, [ray-split reduction], compaction: counts[0] = n'
+int stage_mlp(const VolCall& c);        // the fused program by (c.image, c.nseg, c.o.precision)
+int stage_alpha_ind(const VolCall& c);  // reads R, o.chunk, o.train_th, ws, L, s, split: counts[1] = m
+// reads near_, far_, o.t_rand, raw, s, nseg; n_rays in rays (c.R / nseg under nseg > 0)
+int stage_composite(const VolCall& c, int n_rays, const anr_render_out* out);
 
 }  // namespace anr

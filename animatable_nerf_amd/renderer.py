@@ -21,14 +21,22 @@ import torch
 
 from . import _lib
 from . import config as _config
+from .renderer_knn import _f32, render_precision
 
 CHUNK = 2048  # tpose_renderer.py:170
 RAY_KEYS = ('ray_o', 'ray_d', 'near', 'far')
 FRAME_KEYS = ('A', 'R', 'Th', 'pbw', 'pbounds', 'tbw', 'tbounds')
+# the library's (counts accessor, alpha_ind row gather) of a render workspace and of a Network.forward one
+RENDER_ROWS = ('anr_render_counts', 'anr_render_bw_rows')
+NETWORK_ROWS = ('anr_network_counts', 'anr_network_bw_rows')
 
 
-def _f32(t, device):
-    return t.to(device=device, dtype=torch.float32).contiguous()
+def _read_counts(ws, counts_fn, n):
+    """(kept samples, alpha_ind rows) of workspace ``ws`` through the library's accessor ``counts_fn(ws, n)``:
+    a host read, which waits for the current stream."""
+    off = counts_fn(_lib.ptr(ws), n) - ws.data_ptr()
+    c = ws[off:off + 8].view(torch.int32).cpu()
+    return int(c[0]), int(c[1])
 
 
 class _Call:
@@ -92,12 +100,7 @@ class _Call:
         if prec not in precs:
             raise ValueError(f"train_precision must be one of {sorted(precs)}, got {prec!r}")
         o.precision = precs[prec]
-        self.render_precision = _lib.FP32
-        rprec = cfg.get('render_precision', 'fp32')
-        rprecs = {'fp32': _lib.FP32, 'bf16x3': _lib.BF16X3, 'bf16x6': _lib.BF16X6}
-        if rprec not in rprecs:
-            raise ValueError(f"render_precision must be one of {sorted(rprecs)}, got {rprec!r}")
-        self.render_precision = rprecs[rprec]
+        self.render_precision = render_precision(cfg)
         self.opts = o
         if samples is not None:
             return
@@ -165,28 +168,28 @@ class Renderer:
         return ws
 
     def _counts(self, ws, R):
-        addr = self.lib.anr_render_counts(_lib.ptr(ws), R)
-        base = ws.data_ptr()
-        c = ws[addr - base:addr - base + 8].view(torch.int32).cpu()  # host sync
-        self.last_counts = (int(c[0]), int(c[1]))
+        self.last_counts = _read_counts(ws, self.lib.anr_render_counts, R)
         return self.last_counts
 
-    def _gather_rows(self, ws, R, pbw, tbw, dev, ns=64):
-        """the alpha_ind rows of a workspace of R rays at ns samples into pbw / tbw (64: anr_render_bw_rows,
-        else the entry of the other sample counts)"""
+    def _gather_rows(self, ws, R, pbw, tbw, dev, ns=64, entry=RENDER_ROWS[1]):
+        """the alpha_ind rows of a workspace of R rays at ns samples into pbw / tbw (64: ``entry``, else the
+        entry of the other sample counts)"""
         if ns == 64:
-            _lib.check(self.lib.anr_render_bw_rows(_lib.ptr(ws), R, _lib.ptr(pbw), _lib.ptr(tbw), _lib.stream_ptr(dev)),
-                       'anr_render_bw_rows')
+            _lib.check(getattr(self.lib, entry)(_lib.ptr(ws), R, _lib.ptr(pbw), _lib.ptr(tbw), _lib.stream_ptr(dev)),
+                       entry)
         else:
             _lib.check(self.lib.anr_render_ns_bw_rows(_lib.ptr(ws), R, ns, _lib.ptr(pbw), _lib.ptr(tbw),
                                                       _lib.stream_ptr(dev)), 'anr_render_ns_bw_rows')
 
-    def _bw_rows(self, ws, R, dev, ns=64):
-        _, m = self._counts(ws, R)
+    def _bw_rows(self, ws, R, dev, ns=64, entries=RENDER_ROWS):
+        """(pbw, tbw) alpha_ind rows (1, m, 24) of a workspace of R rays (NETWORK_ROWS: of R free samples); the
+        count read is a host sync (the reference's alpha_ind) and sets last_counts"""
+        self.last_counts = _read_counts(ws, getattr(self.lib, entries[0]), R)
+        m = self.last_counts[1]
         pbw = torch.empty((1, m, 24), device=dev)
         tbw = torch.empty((1, m, 24), device=dev)
         if m > 0:
-            self._gather_rows(ws, R, pbw, tbw, dev, ns)
+            self._gather_rows(ws, R, pbw, tbw, dev, ns, entries[1])
         return pbw, tbw
 
     def _last_device_ws(self, what):
@@ -327,27 +330,51 @@ class Renderer:
         ws = self._render_fwd(c, p, R, attr, image_only)
         return c, ws, R
 
+    # ---- what the two overlapped host renders share ----
+    _PIN = dict(dtype=torch.float32, pin_memory=True)
+
+    def _side_stream(self, dev):
+        """the renderer's copy stream (created on first use) and the current stream of `dev`"""
+        if getattr(self, '_copy_stream', None) is None:
+            self._copy_stream = torch.cuda.Stream(dev)
+        return self._copy_stream, torch.cuda.current_stream(dev)
+
+    def _host_frame(self, R, ns):
+        """page-locked buffers of a frame's four image outputs"""
+        pin = self._PIN
+        return {'rgb_map': torch.empty((1, R, 3), **pin), 'acc_map': torch.empty((1, R), **pin),
+                'depth_map': torch.empty((1, R), **pin), 'raw': torch.empty((1, R * ns, 4), **pin)}
+
+    @staticmethod
+    def _part_batch(batch, a, b):
+        """the batch of rays [a, b): the per-ray tensors sliced, everything else as it is"""
+        from .parallel import RAY_KEYS as SLICED
+        return {key_: (v[:, a:b] if key_ in SLICED and torch.is_tensor(v) else v) for key_, v in batch.items()}
+
+    @staticmethod
+    def _copy_part(h, c, a, b, ns):
+        """call `c`'s four outputs (rays [a, b)) into the frame's host buffers, on the current stream"""
+        h['rgb_map'][:, a:b].copy_(c.rgb, non_blocking=True)
+        h['acc_map'][:, a:b].copy_(c.acc, non_blocking=True)
+        h['depth_map'][:, a:b].copy_(c.depth, non_blocking=True)
+        h['raw'][:, a * ns:b * ns].copy_(c.raw, non_blocking=True)
+
     def _render_overlapped_image(self, batch, R, chunk, parts):
         """_render_overlapped under render_image_only: the same parts of whole chunks on two alternating
         workspaces, part k's four image outputs crossing to page-locked host buffers on the side stream
         while part k + 1 renders. No row buffers, no row extraction, no per-part count read."""
-        from .parallel import RAY_KEYS as SLICED, shard_chunks
+        from .parallel import shard_chunks
         dev = self.device()
         ns = int(self.cfg.N_samples)
         with torch.cuda.device(dev):
-            if getattr(self, '_copy_stream', None) is None:
-                self._copy_stream = torch.cuda.Stream(dev)
-            cs = self._copy_stream
-            cur = torch.cuda.current_stream(dev)
-            pin = dict(dtype=torch.float32, pin_memory=True)
-            h = {'rgb_map': torch.empty((1, R, 3), **pin), 'acc_map': torch.empty((1, R), **pin),
-                 'depth_map': torch.empty((1, R), **pin), 'raw': torch.empty((1, R * ns, 4), **pin)}
+            cs, cur = self._side_stream(dev)
+            h = self._host_frame(R, ns)
             keep = []  # the parts' device tensors, alive until their copies are done
             for k in range(parts):
                 a, b = shard_chunks(R, k, parts, chunk)
                 if a >= b:
                     continue
-                sub = {key_: (v[:, a:b] if key_ in SLICED and torch.is_tensor(v) else v) for key_, v in batch.items()}
+                sub = self._part_batch(batch, a, b)
                 # a part's outputs are its own tensors and nothing is read back from its workspace, so the
                 # next part on the same workspace needs no wait beyond the stream's own order
                 c, _, _ = self._render_launch(sub, '_ws' if k % 2 == 0 else '_ws_b', image_only=True)
@@ -355,10 +382,7 @@ class Renderer:
                 launched.record(cur)
                 with torch.cuda.stream(cs):
                     cs.wait_event(launched)
-                    h['rgb_map'][:, a:b].copy_(c.rgb, non_blocking=True)
-                    h['acc_map'][:, a:b].copy_(c.acc, non_blocking=True)
-                    h['depth_map'][:, a:b].copy_(c.depth, non_blocking=True)
-                    h['raw'][:, a * ns:b * ns].copy_(c.raw, non_blocking=True)
+                    self._copy_part(h, c, a, b, ns)
                 keep.append(c)
             cs.synchronize()
             cur.wait_stream(cs)
@@ -378,17 +402,13 @@ class Renderer:
         tensors are its first m rows (contiguous; no capacity-sized host buffer, no host concatenation).
         A frame whose rows outgrow the buffer moves the placed rows into an exact-size one (one host
         copy) and the rest from the device."""
-        from .parallel import RAY_KEYS as SLICED, shard_chunks
+        from .parallel import shard_chunks
         dev = self.device()
         ns = int(self.cfg.N_samples)
+        pin = self._PIN
         with torch.cuda.device(dev):
-            if getattr(self, '_copy_stream', None) is None:
-                self._copy_stream = torch.cuda.Stream(dev)
-            cs = self._copy_stream
-            cur = torch.cuda.current_stream(dev)
-            pin = dict(dtype=torch.float32, pin_memory=True)
-            h = {'rgb_map': torch.empty((1, R, 3), **pin), 'acc_map': torch.empty((1, R), **pin),
-                 'depth_map': torch.empty((1, R), **pin), 'raw': torch.empty((1, R * ns, 4), **pin)}
+            cs, cur = self._side_stream(dev)
+            h = self._host_frame(R, ns)
             st = dict(late=[], kept=0, off=0, hp=None, ht=None, keep=[], k=0)
             self._last_ws = None  # the parts alternate between two workspaces (row_ids / counts refuse)
             self._last_image_only = False
@@ -401,9 +421,7 @@ class Renderer:
                 a, b, c, ws, Rp, launched, slot = part
                 with torch.cuda.stream(cs):
                     cs.wait_event(launched)  # this part only (the next one is queued behind it on cur)
-                    addr = self.lib.anr_render_counts(_lib.ptr(ws), Rp)
-                    cnt = ws[addr - ws.data_ptr():addr - ws.data_ptr() + 8].view(torch.int32).cpu()  # host read
-                    kept_k, n = int(cnt[0]), int(cnt[1])
+                    kept_k, n = _read_counts(ws, self.lib.anr_render_counts, Rp)  # host read
                     pr = torch.empty((1, n, 24), device=dev)
                     tr = torch.empty((1, n, 24), device=dev)
                     if n:
@@ -417,10 +435,7 @@ class Renderer:
                         cap = int(guess * self.ROWS_HEADROOM) + 64
                         st['hp'] = torch.empty((1, cap, 24), **pin)
                         st['ht'] = torch.empty((1, cap, 24), **pin)
-                    h['rgb_map'][:, a:b].copy_(c.rgb, non_blocking=True)
-                    h['acc_map'][:, a:b].copy_(c.acc, non_blocking=True)
-                    h['depth_map'][:, a:b].copy_(c.depth, non_blocking=True)
-                    h['raw'][:, a * ns:b * ns].copy_(c.raw, non_blocking=True)
+                    self._copy_part(h, c, a, b, ns)
                     off, hp, ht = st['off'], st['hp'], st['ht']
                     if n and hp is not None and off + n <= hp.shape[1] and not st['late']:
                         hp[:, off:off + n].copy_(pr, non_blocking=True)
@@ -440,7 +455,7 @@ class Renderer:
                 slot = k % 2
                 if ws_free[slot] is not None:
                     cur.wait_event(ws_free[slot])  # the workspace's previous part has its rows out
-                sub = {key_: (v[:, a:b] if key_ in SLICED and torch.is_tensor(v) else v) for key_, v in batch.items()}
+                sub = self._part_batch(batch, a, b)
                 c, ws, Rp = self._render_launch(sub, '_ws' if slot == 0 else '_ws_b')
                 launched = torch.cuda.Event()
                 launched.record(cur)
@@ -502,21 +517,8 @@ class Renderer:
             _lib.check(self.lib.anr_network_fwd(ctypes.byref(p), ctypes.byref(c.frame), ctypes.byref(c.samples),
                                                 ctypes.byref(c.opts), _lib.ptr(raw), _lib.ptr(ws), ws_bytes,
                                                 _lib.stream_ptr(dev)), 'anr_network_fwd')
-            pbw, tbw = self._net_rows(ws, c.n, dev)
+            pbw, tbw = self._bw_rows(ws, c.n, dev, entries=NETWORK_ROWS)
         return {'pbw': pbw, 'tbw': tbw, 'raw': raw}
-
-    def _net_rows(self, ws, n, dev):
-        addr = self.lib.anr_network_counts(_lib.ptr(ws), n)
-        base = ws.data_ptr()
-        cnt = ws[addr - base:addr - base + 8].view(torch.int32).cpu()  # host sync (the reference's alpha_ind)
-        self.last_counts = (int(cnt[0]), int(cnt[1]))
-        m = self.last_counts[1]
-        pbw = torch.empty((1, m, 24), device=dev)
-        tbw = torch.empty((1, m, 24), device=dev)
-        if m > 0:
-            _lib.check(self.lib.anr_network_bw_rows(_lib.ptr(ws), n, _lib.ptr(pbw), _lib.ptr(tbw), _lib.stream_ptr(dev)),
-                       'anr_network_bw_rows')
-        return pbw, tbw
 
     def blend_weights(self, pts, smpl_bw, latent_index, field=0, row_add=0):
         """calculate_neural_blend_weights (field 0, tpose_nerf_network.py:55-77) / novel_pose_bw (field 1,
@@ -581,6 +583,14 @@ def _cfg_deterministic(cfg):
     return True if cfg.get('train_deterministic', False) else None
 
 
+def _grad_buffers(params, upstream):
+    """a backward's buffers: zeroed gradients of `params`, their pointer array for the library, and the
+    upstream gradients made contiguous (None stays None)"""
+    grads = [torch.zeros_like(t) for t in params]
+    gp = (ctypes.c_void_p * _lib.NUM_TENSORS)(*[g.data_ptr() for g in grads])
+    return grads, gp, [t.contiguous() if t is not None else None for t in upstream]
+
+
 class _TrainRender(torch.autograd.Function):
     """forward = anr_train_fwd, backward = anr_train_bwd (parameter gradients accumulate)."""
 
@@ -611,9 +621,7 @@ class _TrainRender(torch.autograd.Function):
         params = r.net.core_tensors()
         dev = params[0].device
         p = r.params(pack=False)
-        grads = [torch.zeros_like(t) for t in params]
-        gp = (ctypes.c_void_p * _lib.NUM_TENSORS)(*[g.data_ptr() for g in grads])
-        keep = [t.contiguous() if t is not None else None for t in (d_rgb, d_pbw, d_tbw)]
+        grads, gp, keep = _grad_buffers(params, (d_rgb, d_pbw, d_tbw))
         with _lib.deterministic(_cfg_deterministic(r.cfg)):
             rc = lib.anr_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), *c.ray_ptrs(), c.R,
                                    ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),
@@ -638,7 +646,7 @@ class _TrainNetwork(torch.autograd.Function):
         _lib.check(lib.anr_network_train_fwd(ctypes.byref(p), ctypes.byref(c.frame), ctypes.byref(c.samples),
                                              ctypes.byref(c.opts), _lib.ptr(raw), _lib.ptr(ws), ws_bytes,
                                              _lib.stream_ptr(dev)), 'anr_network_train_fwd')
-        pbw, tbw = renderer._net_rows(ws, c.n, dev)
+        pbw, tbw = renderer._bw_rows(ws, c.n, dev, entries=NETWORK_ROWS)
         ctx.renderer, ctx.call, ctx.ws, ctx.ws_bytes = renderer, c, ws, ws_bytes
         return raw, pbw, tbw
 
@@ -648,9 +656,7 @@ class _TrainNetwork(torch.autograd.Function):
         params = r.net.core_tensors()
         dev = params[0].device
         p = r.params(pack=False)
-        grads = [torch.zeros_like(t) for t in params]
-        gp = (ctypes.c_void_p * _lib.NUM_TENSORS)(*[g.data_ptr() for g in grads])
-        keep = [t.contiguous() if t is not None else None for t in (d_raw, d_pbw, d_tbw)]
+        grads, gp, keep = _grad_buffers(params, (d_raw, d_pbw, d_tbw))
         with _lib.deterministic(_cfg_deterministic(r.cfg)):
             rc = r.lib.anr_network_train_bwd(ctypes.byref(p), gp, ctypes.byref(c.frame), ctypes.byref(c.samples),
                                              ctypes.byref(c.opts), *[_lib.ptr(t) for t in keep], _lib.ptr(ctx.ws),

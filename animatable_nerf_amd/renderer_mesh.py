@@ -130,11 +130,7 @@ class Renderer(_renderer.Renderer):
         o.chunk_pts = int(chunk_pts)
         o.norm_th = MESH_NORM_TH
         o.novel_pose = 1 if self.cfg.get('test_novel_pose', False) else 0
-        rprec = self.cfg.get('render_precision', 'fp32')
-        rprecs = {'fp32': _lib.FP32, 'bf16x3': _lib.BF16X3, 'bf16x6': _lib.BF16X6}
-        if rprec not in rprecs:
-            raise ValueError(f"render_precision must be one of {sorted(rprecs)}, got {rprec!r}")
-        o.precision = rprecs[rprec]
+        o.precision = _renderer.render_precision(self.cfg)
         nbytes = self.lib.anr_alpha_workspace_bytes(n, ctypes.byref(o), ctypes.byref(f))
         if nbytes == 0:
             raise ValueError('anr_alpha_workspace_bytes: bad arguments (chunk_pts must be a multiple of 64)')
